@@ -12,8 +12,11 @@ region, in GiB/s.
 
 The printed line is the C2 workload (BASELINE configs[1]: 4096 independent
 64 KiB pairs per GPU, 1% byte substitutions, --table-size 1 -> q = 4099).
-Beside it, under "also", the same run measures the other BASELINE configs on
-the same ranks, each with its own roofline and CPU baseline:
+A plain run measures that line alone: set up, a checked step, the settling
+and W warmup steps, the K timed steps, the result line.  With --full the same
+run also takes the untimed stage-profile pass and the CPU baseline of the
+line and measures, under "also", the other BASELINE configs on the same
+ranks, each with its own roofline and CPU baseline:
   c3  8192 x 256 KiB pairs per GPU, 10% edits, onepass, q = 16411 (the config
       BASELINE shards over 8 GPUs: 65536 pairs on 8);
   c4  4096 transposition pairs of ~256 KiB per GPU, correcting;
@@ -22,7 +25,11 @@ the same ranks, each with its own roofline and CPU baseline:
 Inputs are synthetic and generated on the device (DESIGN.md "Synthetic
 inputs").  Pairs shard across ranks by contiguous index ranges (weak scaling).
 
-Launch: python bench.py [--gpus N --steps K --warmup W].  With N > 1 and no
+--dump-outputs DIR writes what the last timed step of the printed line left in
+the caller's buffers as DIR/<name>.npy (dump_outputs below); the inputs are
+seeded, so two builds of the library can be compared output for output.
+
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full].  With N > 1 and no
 WORLD_SIZE in the environment, bench.py starts torch.distributed.run with N
 ranks itself (before any GPU call); under torch.distributed.run it runs as
 one rank per GPU (RCCL over xGMI).  --dry-run brings the ranks up over gloo on
@@ -108,6 +115,12 @@ HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICR
 # step only: each event costs its stream ~3.5 us (C2's two per step cost the
 # line ~1.5 %); the average launch time comes from those sampled launches.
 TIMING_EVERY = 4
+# --full with a large --steps (a K sized for the C2 step, 0.27 ms) stays inside
+# its ten minutes: the configs under "also", whose steps take up to 60 ms, time
+# at most the default K and W, and the stage-profile pass keeps the events of
+# its last PROFILE_RING steps.  Up to the defaults nothing changes.
+ALSO_MAX_STEPS, ALSO_MAX_WARMUP = 100, 20
+PROFILE_RING = 200
 
 
 def timing_ring(steps, every=TIMING_EVERY):
@@ -346,6 +359,39 @@ def make_inputs(dg, ctx, torch, name, lo, n, stream):
     return ref, ver, [(x.r_off, x.r_len, x.v_off, x.v_len) for x in pairs[:n]]
 
 
+DUMP_BYTES = 8 << 20   # arena bytes kept by --dump-outputs (as float32: 32 MiB of the 64 MB allowed)
+
+
+def dump_outputs(path, R, arena, spans, arrays):
+    """--dump-outputs: what the last timed step left in the caller's buffers,
+    as <path>/<name>.npy (float32 / float64; <name>.rank<r>.npy at N > 1).
+    `arrays` (name -> (tensor, dtype)) are written whole.  `arena` is the packed
+    u8 output and `spans` its (offset, length) per stream: whole streams are
+    kept in a seeded order (a permutation of the stream indices, the same for
+    every build) until DUMP_BYTES are reached; <arena name>_streams lists them."""
+    import numpy as np
+    torch = R.torch
+    os.makedirs(path, exist_ok=True)
+
+    def save(name, a):
+        np.save(os.path.join(path, name + (f".rank{R.rank}" if R.world > 1 else "") + ".npy"), a)
+
+    for name, (t, dt) in arrays.items():
+        save(name, t.cpu().numpy().astype(dt))
+    name, buf = arena
+    order = np.random.RandomState(0x0D5E).permutation(len(spans))
+    keep, total = [], 0
+    for i in order:
+        if keep and total + spans[i][1] > DUMP_BYTES:
+            break
+        keep.append(int(i))
+        total += min(spans[i][1], DUMP_BYTES)
+    parts = [buf[spans[i][0]:spans[i][0] + min(spans[i][1], DUMP_BYTES)] for i in keep]
+    sample = torch.cat(parts) if parts else buf[:0]
+    save(name, sample.cpu().numpy().astype(np.float32))
+    save(name + "_streams", np.asarray(keep, dtype=np.float64))
+
+
 def timed(R, args, step):
     """W untimed steps, then exactly K steps bracketed by barrier + synchronize;
     returns the max-over-ranks wall time of the K steps."""
@@ -360,7 +406,7 @@ def timed(R, args, step):
     return time.perf_counter() - t0
 
 
-def bench_encode(name, args, R, dg, ctx, shard, stream):
+def bench_encode(name, args, R, dg, ctx, shard, stream, dump=None):
     torch = R.torch
     cfg = CONFIGS[name]
     npg, L, rate, q, seed_base, desc, algo = cfg
@@ -415,20 +461,23 @@ def bench_encode(name, args, R, dg, ctx, shard, stream):
             raise SystemExit(f"{name}: global output index inconsistent")
     yield None   # prepared: the caller decides when the measurement runs
 
-    # The stage breakdown first: an untimed pass with every stage event, over
-    # at least K steps and ~50 ms of GPU time.  It also brings the plan to its
-    # steady state: a fresh C2 plan runs its first ~40 steps ~12 % slower
-    # (scripts/step_diag.py: the same with 4 input batches in turn, so not the
-    # Infinity Cache, and after unrelated GPU load, so not the clocks).
+    # The settling pass first: untimed, at least K steps and ~50 ms of GPU
+    # time.  It brings the plan to its steady state: a fresh C2 plan runs its
+    # first ~40 steps ~12 % slower (scripts/step_diag.py: the same with 4 input
+    # batches in turn, so not the Infinity Cache, and after unrelated GPU load,
+    # so not the clocks).  With --full it records every stage event: the
+    # stage breakdown of the line (stage_ms_profile).
+    full_run = getattr(args, "full", True)   # (scripts/ab_bench.py's args have no --full: it keeps the profile)
     n_prof = max(args.steps, min(200, int(0.05 / max(t_chk, 1e-6))))
-    plan.set_timing(n_prof)
+    plan.set_timing(min(n_prof, PROFILE_RING) if full_run else 0)   # (the ring keeps the pass's last runs)
     for _ in range(n_prof):
         step()
-    profile = plan.stage_times()
+    profile = plan.stage_times() if full_run else None
 
     # In the timed steps only the events around the dominant kernel(s) are
-    # recorded; the full stage breakdown comes from an untimed pass of the
-    # same steps afterwards.  (The ring keeps the last K runs: the timed ones.)
+    # recorded; the full stage breakdown comes from the untimed pass of the
+    # same steps before them (--full).  (The ring keeps the last K runs: the
+    # timed ones.)
     timing = getattr(args, "stage_timing", "dominant")
     every, slots = timing_ring(args.steps, getattr(args, "timing_every", TIMING_EVERY))
     if timing != "none":
@@ -443,6 +492,10 @@ def bench_encode(name, args, R, dg, ctx, shard, stream):
     stages = plan.stage_times() if timing != "none" else {}
     plan.set_timing(0)
     elapsed = shard.max_over_ranks(R.dist, elapsed, R.world, "cuda")
+    if dump:   # the packed deltas, their offsets and the per-pair status of the last timed step
+        o = offs.cpu().tolist()
+        dump_outputs(dump, R, ("delta_bytes", out), [(o[i], o[i + 1] - o[i]) for i in range(n)],
+                     {"offsets": (offs, "float64"), "status": (status, "float32")})
 
     in_bytes_rank = sum(rl + vl for _, rl, _, vl in layout)
     in_bytes_job = shard.sum_over_ranks(R.dist, in_bytes_rank, R.world, "cuda")
@@ -545,9 +598,6 @@ def bench_encode(name, args, R, dg, ctx, shard, stream):
                        "HIP events on the run stream around the onepass kernel, mean over the timed "
                        "steps (the only events recorded in them)"),
             "stage_ms": {k: round(v, 4) for k, v in stages.items()},
-            "stage_ms_profile": {k: round(v, 4) for k, v in profile.items()},
-            "stage_ms_profile_note": (f"every stage event, an untimed pass of {n_prof} steps before the W warmup "
-                                      "and K timed steps"),
             "path_bytes_per_step": path_bytes,
             "path_bytes": "sum(|R|+|V|) + sum|delta| per rank (SURVEY 8(d))",
             "path_achieved": round(path_bytes / step_s / 1e9, 2),
@@ -556,6 +606,11 @@ def bench_encode(name, args, R, dg, ctx, shard, stream):
         "cpu_baseline": None,
         "lib_sha16": lib_sha16(),
     }
+    if profile is not None:
+        line["roofline"]["stage_ms_profile"] = {k: round(v, 4) for k, v in profile.items()}
+        line["roofline"]["stage_ms_profile_note"] = (f"every stage event, the last {min(n_prof, PROFILE_RING)} steps "
+                                                     f"of an untimed pass of {n_prof} steps before the W warmup "
+                                                     "and K timed steps")
     if npg == CONFIGS[name][0]:
         pt, pt_src = pmc_path(name)
         rl = line["roofline"]
@@ -574,7 +629,7 @@ def bench_encode(name, args, R, dg, ctx, shard, stream):
     torch.cuda.empty_cache()
 
 
-def bench_decode(name, args, R, dg, ctx, shard, stream):
+def bench_decode(name, args, R, dg, ctx, shard, stream, dump=None):
     """C5 / C5o: in-place deltas of this rank's pairs are produced first
     (untimed: device onepass (C2 pairs) or correcting (C4 transposition
     pairs) encode, then dg_make_inplace(localmin) on the host, as `delta
@@ -649,6 +704,10 @@ def bench_decode(name, args, R, dg, ctx, shard, stream):
     elapsed = timed(R, args, step)
     stages = plan.stage_times()
     elapsed = shard.max_over_ranks(R.dist, elapsed, R.world, "cuda")
+    if dump:   # the reconstructed streams, their lengths and the per-stream status of the last timed step
+        lens = out_len.cpu().tolist()
+        dump_outputs(dump, R, ("output_bytes", out), [(d[4], min(int(lens[i]), d[5])) for i, d in enumerate(descs)],
+                     {"out_len": (out_len, "float64"), "status": (status, "float32")})
     v_bytes = sum(vl for _, _, _, vl in layout)
     v_bytes_job = shard.sum_over_ranks(R.dist, v_bytes, R.world, "cuda")
     d_bytes = d_offs[-1]
@@ -788,12 +847,13 @@ def bench_e2e(args, R, dg, ctx, stream):
     return line
 
 
-def prepare_config(name, args, R, dg, ctx, shard, stream):
+def prepare_config(name, args, R, dg, ctx, shard, stream, dump=None):
     """The config's inputs, plan and a checked step; returns (measure,
     release): measure() runs the W warmup and K timed steps and returns the
-    line, release() frees the config's device memory."""
+    line (and writes the last step's outputs under `dump`, if given),
+    release() frees the config's device memory."""
     fn = bench_decode if CONFIGS[name][6] == "decode" else bench_encode
-    g = fn(name, args, R, dg, ctx, shard, stream)
+    g = fn(name, args, R, dg, ctx, shard, stream, dump)
     next(g)
     return (lambda: next(g)), (lambda: next(g, None))
 
@@ -966,15 +1026,22 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="beside the printed line: its untimed stage-profile pass and CPU baseline, the "
+                         "--also configs and the host-to-host line (a plain run measures the line alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (packed deltas or decoded "
+                         "streams, offsets / lengths, status) as DIR/<name>.npy")
     ap.add_argument("--also", default="c3,c4,c5,c5o,c6,c2_defq,c3s,c3s_chain,c4o,c4o_chain",
-                    help="extra configs measured in the same run, reported under 'also' "
+                    help="with --full: extra configs measured in the same run, reported under 'also' "
                          "('none' to skip)")
     ap.add_argument("--pairs", type=int, default=0, help="override pairs per GPU")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-e2e", dest="e2e", action="store_false",
                     help="skip the host-to-host line (also.e2e_c2: dg_encode_pipelined, 16384 pinned C2 pairs)")
-    ap.add_argument("--full-out", default=os.path.join(ROOT, "gpurun_out", "bench_full.json"),
-                    help="where the full detail of every line goes (the printed line is compact)")
+    ap.add_argument("--full-out", default=None,
+                    help="where the full detail of every line goes (the printed line is compact); with --full "
+                         "and no path: bench_out/bench_full.json beside this file, where that can be written")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher/orchestration check on the CPU over gloo (no GPU)")
     args = ap.parse_args()
@@ -1008,19 +1075,22 @@ def main():
     # (the checked step, the stage-profile pass, W warmup: `untimed_steps`)
     # cover that, and the headline measured first reads the same as measured
     # last (C2 1734 / 1720 alone vs 1721 last, one box, round 4).
-    extras = [c for c in args.also.split(",") if c and c != "none" and c != args.config]
-    head_measure, head_release = prepare_config(args.config, args, R, dg, ctx, shard, stream)
+    extras = [c for c in args.also.split(",") if c and c != "none" and c != args.config] if args.full else []
+    head_measure, head_release = prepare_config(args.config, args, R, dg, ctx, shard, stream,
+                                                dump=args.dump_outputs)
     line = head_measure()
     head_release()
     also, release = {}, None
+    also_args = argparse.Namespace(**dict(vars(args), steps=min(args.steps, ALSO_MAX_STEPS),
+                                          warmup=min(args.warmup, ALSO_MAX_WARMUP)))
     for name in extras:
         if release:
             release()
-        measure, release = prepare_config(name, args, R, dg, ctx, shard, stream)
+        measure, release = prepare_config(name, also_args, R, dg, ctx, shard, stream)
         also[name] = measure()
     if release:
         release()
-    if args.e2e and world == 1 and args.config == "c2":
+    if args.full and args.e2e and world == 1 and args.config == "c2":
         # (only beside the C2 headline, and a box without the
         # pinned memory reports the failure in the line instead of aborting)
         try:
@@ -1028,17 +1098,28 @@ def main():
         except Exception as e:  # noqa: BLE001
             torch.cuda.synchronize()
             also["e2e_c2"] = {"value": None, "error": f"{type(e).__name__}: {e}"[:200]}
-    add_cpu_baseline(args.config, line, args, R)
+    if args.full:
+        add_cpu_baseline(args.config, line, args, R)
     for name in extras:
         add_cpu_baseline(name, also[name], args, R)
     if rank == 0:
         full = dict(line, also=also) if also else line
-        path = args.full_out
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        with open(path, "w") as f:
-            json.dump(full, f, indent=1)
-        print(f"bench.py: every field of every line in {path}", file=sys.stderr, flush=True)
-        print(compact_line(line, also or None, os.path.relpath(path, ROOT)), flush=True)
+        # the detail file: where --full-out says (a plain run writes none
+        # without it); a --full run without it tries its default place, and a
+        # tree that cannot be written to costs the file, not the line
+        path = args.full_out or (os.path.join(ROOT, "bench_out", "bench_full.json") if args.full else None)
+        if path:
+            try:
+                os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+                with open(path, "w") as f:
+                    json.dump(full, f, indent=1)
+                print(f"bench.py: every field of every line in {path}", file=sys.stderr, flush=True)
+            except OSError as e:
+                if args.full_out:
+                    raise
+                print(f"bench.py: detail file not written ({e})", file=sys.stderr, flush=True)
+                path = None
+        print(compact_line(line, also or None, os.path.relpath(path, ROOT) if path else None), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

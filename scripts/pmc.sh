@@ -2,7 +2,7 @@
 # PMC passes over a short bench run (one counter group per pass; no sys/runtime trace).
 set -o pipefail
 OUT=${1:-gpurun_out/pmc}
-ARGS=${2:---steps 3 --warmup 1 --no-cpu-baseline}
+ARGS=${2:---full --steps 3 --warmup 1 --no-cpu-baseline}
 export TMPDIR=/tmp
 i=0
 for grp in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU" \

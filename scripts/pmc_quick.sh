@@ -3,7 +3,7 @@
 # usage: scripts/pmc_quick.sh OUTDIR "bench args"
 set -o pipefail
 OUT=${1:-gpurun_out/pmcq}
-ARGS=${2:---steps 3 --warmup 1 --no-cpu-baseline}
+ARGS=${2:---full --steps 3 --warmup 1 --no-cpu-baseline}
 export TMPDIR=/tmp
 mkdir -p $OUT
 i=0
