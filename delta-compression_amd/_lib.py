@@ -407,8 +407,9 @@ def encode(R: bytes, V: bytes, algorithm="onepass", p: int = SEED_LEN, q: int = 
 
 def encode_batch(pairs: Sequence[Tuple[bytes, bytes]], algorithm="onepass", p: int = SEED_LEN,
                  q: int = TABLE_SIZE, buf_cap: int = BUF_CAP, max_table: int = MAX_TABLE_SIZE,
-                 ctx: Optional[Context] = None) -> List[bytes]:
-    """Many pairs through the batched device path (host buffers in and out)."""
+                 ctx: Optional[Context] = None, splay: bool = False) -> List[bytes]:
+    """Many pairs through the batched device path (host buffers in and out).
+    splay: greedy's tie-break among the longest matches (smallest offset)."""
     ctx = ctx or default_context()
     n = len(pairs)
     if n == 0:
@@ -420,7 +421,7 @@ def encode_batch(pairs: Sequence[Tuple[bytes, bytes]], algorithm="onepass", p: i
     vl = (C.c_size_t * n)(*[len(v) for _, v in keep])
     outs = (Buffer * n)()
     st = (C.c_int32 * n)()
-    o = _opts(p, q, buf_cap, max_table)
+    o = _opts(p, q, buf_cap, max_table, splay=splay)
     ctx.check(lib.dg_encode_batch(ctx.handle, _algo(algorithm), rp, rl, vp, vl, n, C.byref(o), outs,
                                   st), "dg_encode_batch")
     res = []
@@ -435,7 +436,8 @@ def encode_batch(pairs: Sequence[Tuple[bytes, bytes]], algorithm="onepass", p: i
 def encode_pipelined(pairs: Sequence[Tuple[bytes, bytes]], algorithm="onepass", p: int = SEED_LEN,
                      q: int = TABLE_SIZE, buf_cap: int = BUF_CAP, max_table: int = MAX_TABLE_SIZE,
                      chunk_bytes: int = 0, pinned: bool = False, align: int = 16, out_cap: Optional[int] = None,
-                     ctx: Optional[Context] = None, ctxs: Optional[Sequence[Context]] = None) -> List[bytes]:
+                     ctx: Optional[Context] = None, ctxs: Optional[Sequence[Context]] = None,
+                     splay: bool = False) -> List[bytes]:
     """Many pairs host-to-host through dg_encode_pipelined (chunked, two chunks in
     flight).  The pairs are laid out in host arenas `align` bytes apart, pinned
     (dg_host_alloc) or pageable (bytearray).  ctxs: one context per device,
@@ -471,7 +473,7 @@ def encode_pipelined(pairs: Sequence[Tuple[bytes, bytes]], algorithm="onepass", 
         pa = (Pair * n)(*[Pair(*x) for x in lay])
         offs = (C.c_uint64 * (n + 1))()
         st = (C.c_int32 * n)()
-        o = _opts(p, q, buf_cap, max_table)
+        o = _opts(p, q, buf_cap, max_table, splay=splay)
         if ctxs:
             hs = (C.c_void_p * len(ctxs))(*[c.handle for c in ctxs])
             ctx.check(lib.dg_encode_pipelined_multi(hs, len(ctxs), _algo(algorithm), hr, hv, pa, n, C.byref(o),
@@ -584,26 +586,32 @@ def _placed_list(cl: Commands) -> list:
 
 def diff(R: bytes, V: bytes, algorithm="onepass", p: int = SEED_LEN, q: int = TABLE_SIZE,
          buf_cap: int = BUF_CAP, max_table: int = MAX_TABLE_SIZE, verbose: bool = False,
-         ctx: Optional[Context] = None) -> list:
-    """delta_diff / diff_onepass / diff_correcting (delta.py:376, 576): the
-    algorithm's commands (CopyCmd / AddCmd), computed by the GPU encoder
-    (dg_diff)."""
-    return unplace_commands(diff_placed(R, V, algorithm, p, q, buf_cap, max_table, verbose, ctx))
+         ctx: Optional[Context] = None, splay: bool = False) -> list:
+    """delta_diff / diff_greedy / diff_onepass / diff_correcting (delta.py:376,
+    576): the algorithm's commands (CopyCmd / AddCmd), computed by the GPU
+    encoder (dg_diff).  splay: greedy only."""
+    return unplace_commands(diff_placed(R, V, algorithm, p, q, buf_cap, max_table, verbose, ctx, splay))
 
 
 def diff_placed(R: bytes, V: bytes, algorithm="onepass", p: int = SEED_LEN, q: int = TABLE_SIZE,
                 buf_cap: int = BUF_CAP, max_table: int = MAX_TABLE_SIZE, verbose: bool = False,
-                ctx: Optional[Context] = None) -> list:
+                ctx: Optional[Context] = None, splay: bool = False) -> list:
     """place_commands(diff(...)) in one call (dg_diff returns the placed form)."""
     ctx = ctx or default_context()
     cl = Commands()
-    o = _opts(p, q, buf_cap, max_table, verbose=verbose)
+    o = _opts(p, q, buf_cap, max_table, verbose=verbose, splay=splay)
     ctx.check(lib.dg_diff(ctx.handle, _algo(algorithm), _u8(R), len(R), _u8(V), len(V), C.byref(o),
                           C.byref(cl)), "dg_diff")
     try:
         return _placed_list(cl)
     finally:
         lib.dg_commands_free(C.byref(cl))
+
+
+def diff_greedy(R: bytes, V: bytes, p: int = SEED_LEN, splay: bool = False, **kw) -> list:
+    """delta_diff_greedy (greedy.c:88-267): the longest match at every position;
+    splay picks the smallest offset among the longest instead of the largest."""
+    return diff(R, V, "greedy", p=p, splay=splay, **kw)
 
 
 def diff_onepass(R: bytes, V: bytes, p: int = SEED_LEN, q: int = TABLE_SIZE, **kw) -> list:

@@ -6,14 +6,15 @@
  * :402-425 info), so scripts that parse it (tests/transposition-benchmark.sh
  * :50-62) keep working.  All compute runs on the GPU through the C ABI.
  *
- *   delta encode <onepass|correcting> <ref> <ver> <delta> [options]
+ *   delta encode <greedy|onepass|correcting> <ref> <ver> <delta> [options]
  *   delta decode <ref> <delta> <output> [--ignore-hash]
  *   delta info <delta>
  *   delta inplace <ref> <delta_in> <delta_out> [--policy localmin|constant]
  *
  * --inplace / inplace run the CRWI conversion on the host (dg_make_inplace,
- * main.c:279-283 and :427-480).  Not provided by this build (exit 1 with a
- * message): the greedy algorithm and --splay.
+ * main.c:279-283 and :427-480).  --splay applies to greedy only (its tie-break
+ * among the longest matches); with onepass or correcting it is not provided
+ * by this build (exit 1 with a message).
  */
 #include <errno.h>
 #include <getopt.h>
@@ -89,7 +90,7 @@ static void usage(void)
 	    "  delta info <delta>\n"
 	    "  delta inplace <ref> <delta_in> <delta_out> [--policy P]\n"
 	    "\n"
-	    "Algorithms: onepass, correcting (MI355X)\n"
+	    "Algorithms: greedy, onepass, correcting (MI355X)\n"
 	    "\n"
 	    "Options:\n"
 	    "  --seed-len N     Seed length (default %d)\n"
@@ -97,7 +98,8 @@ static void usage(void)
 	    "  --max-table N    Max hash table size, k/M/B suffix ok (default %lu)\n"
 	    "  --inplace        Produce in-place delta\n"
 	    "  --policy P       Cycle policy: localmin (default), constant\n"
-	    "  --verbose        Print diagnostics\n",
+	    "  --verbose        Print diagnostics\n"
+	    "  --splay          Use splay tree instead of hash table (greedy only)\n",
 	    DG_SEED_LEN, (unsigned long)DG_TABLE_SIZE, (unsigned long)DG_MAX_TABLE_SIZE);
 	exit(1);
 }
@@ -120,10 +122,8 @@ static int cmd_encode(int argc, char **argv)
 	dg_algorithm_t algo;
 	if (strcmp(algo_str, "onepass") == 0) algo = DG_ALGO_ONEPASS;
 	else if (strcmp(algo_str, "correcting") == 0) algo = DG_ALGO_CORRECTING;
-	else if (strcmp(algo_str, "greedy") == 0) {
-		fprintf(stderr, "greedy is not provided by the MI355X build\n");
-		return 1;
-	} else {
+	else if (strcmp(algo_str, "greedy") == 0) algo = DG_ALGO_GREEDY;
+	else {
 		fprintf(stderr, "Unknown algorithm: %s\n", algo_str);
 		return 1;
 	}
@@ -149,8 +149,12 @@ static int cmd_encode(int argc, char **argv)
 		case 'v': o.flags |= 1ull << DG_OPT_VERBOSE; break;
 		case 'i': o.flags |= 1ull << DG_OPT_INPLACE; break;
 		case 'y':
-			fprintf(stderr, "--splay is not provided by the MI355X build\n");
-			return 1;
+			if (algo != DG_ALGO_GREEDY) {
+				fprintf(stderr, "--splay is not provided by the MI355X build\n");
+				return 1;
+			}
+			o.flags |= 1ull << DG_OPT_SPLAY;
+			break;
 		case 'p':
 			policy_str = optarg;
 			if (strcmp(optarg, "constant") == 0) o.flags |= 1ull << DG_OPT_POLICY_CONSTANT;
@@ -176,10 +180,11 @@ static int cmd_encode(int argc, char **argv)
 	write_file(delta_path, d.data, d.len);
 	dg_delta_info_t inf;
 	dg_delta_info(d.data, d.len, &inf);
+	const char *splay_str = ((o.flags >> DG_OPT_SPLAY) & 1) ? " [splay]" : "";   /* main.c:298-304 */
 	if ((o.flags >> DG_OPT_INPLACE) & 1)
-		printf("Algorithm:    %s + in-place (%s)\n", algo_str, policy_str);
+		printf("Algorithm:    %s%s + in-place (%s)\n", algo_str, splay_str, policy_str);
 	else
-		printf("Algorithm:    %s\n", algo_str);
+		printf("Algorithm:    %s%s\n", algo_str, splay_str);
 	printf("Reference:    %s (%zu bytes)\n", ref_path, rl);
 	printf("Version:      %s (%zu bytes)\n", ver_path, vl);
 	printf("Delta:        %s (%zu bytes)\n", delta_path, d.len);

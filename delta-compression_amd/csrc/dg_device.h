@@ -41,6 +41,9 @@ struct PairPlanDev {
 	uint64_t f_size, f_magic;  // |F| and floor((2^64-1)/|F|)
 	uint64_t m, m_magic;       // checkpoint modulus and Barrett
 	uint64_t tab_base;         // first entry of this pair's R index (correcting)
+	// greedy (dg_greedy.hip) keeps its index geometry in the same words: q = 0,
+	// f_size = bucket count (a power of two), tab_base = first word of the
+	// pair's heads (f_size + 1 words), m = first of its |R| - p + 1 entries
 	// onepass member mode (dg_members.hip)
 	uint64_t mem_base;         // first member slot (n_chunks x kMemChunkSlots slots)
 	uint32_t chunk_base;       // first chunk (index into the per-chunk member counts)
@@ -151,6 +154,25 @@ struct EncodeArgs {
 	uint64_t* crc_out;
 	const uint64_t* crc_tab;   // the context's CRC tables (CrcArgs::tables)
 	const uint64_t* crc_k32;   // x^(8 * 32 * t), t = 0..1023
+};
+
+// greedy (dg_greedy.hip): the CSR seed index over every pair's R and the
+// scan's outputs (records in the onepass layout, kRecWordsOnepass)
+struct GreedyArgs {
+	const uint8_t* ref;
+	const uint8_t* ver;
+	const PairDev* pairs;
+	const PairPlanDev* pplan;
+	uint32_t n_pairs;
+	uint32_t p;
+	uint32_t splay;            // ties among the longest: 0 = largest offset, 1 = smallest (DG_OPT_SPLAY)
+	uint32_t max_seeds;        // max over pairs of |R| - p + 1
+	uint32_t* heads;           // per pair f_size + 1 words from tab_base: bucket b = entries [h[b], h[b + 1])
+	uint2* ent;                // per pair |R| - p + 1 entries from m: (offset, tag), grouped by bucket
+	uint32_t* rec;
+	uint32_t* n_rec;
+	uint64_t* dsize;
+	int32_t* status;
 };
 
 constexpr uint32_t kSegTail = 0xFFFFFFFFu;
@@ -290,6 +312,9 @@ hipError_t launch_member_serialize(const MemSerArgs& a, uint32_t n_chunks, uint3
 hipError_t launch_correcting_clear(const EncodeArgs& a, hipStream_t st);
 hipError_t launch_correcting(const EncodeArgs& a, uint32_t p, hipStream_t st, uint32_t lds_cap, uint64_t qmin,
                              hipEvent_t ev_built, hipEvent_t ev_fork);
+// greedy: zero the heads (head_words in all), build every pair's index, record
+// ev_built (nullable, stage timing), scan
+hipError_t launch_greedy(const GreedyArgs& g, uint64_t head_words, hipStream_t st, hipEvent_t ev_built);
 // (route_cnt / route_fb: the routed-pair count moved to a host-mapped word)
 hipError_t launch_scan(const uint64_t* sz, uint64_t* off, uint32_t n, hipStream_t st,
                        uint32_t* route_cnt = nullptr, uint32_t* route_fb = nullptr);

@@ -429,12 +429,14 @@ struct dg_encode_plan {
 	uint64_t total_rec = 0;
 	uint64_t qmax = 0;
 	uint64_t ctab_entries = 0;   // correcting: sum of per-pair index sizes
+	uint64_t greedy_heads = 0;   // greedy: sum of per-pair head words (buckets + 1), in d_ctab
 	uint64_t max_seeds = 0;
 	uint32_t n_tables = 0;
 	bool aligned16 = true;   // every pair offset a multiple of 16 (LDS-window kernel)
 	// device buffers
 	DevBuf d_pairs, d_pplan, d_powc, d_rec, d_nrec, d_dsize, d_crc_spans_r, d_crc_segs,
-	    d_seg_crc, d_crc, d_tables, d_locks, d_tags, d_ctab, d_lookback, d_kcls, d_gpairs, d_prio_flag;
+	    d_seg_crc, d_crc, d_tables, d_locks, d_tags, d_ctab, d_lookback, d_kcls, d_gpairs, d_prio_flag,
+	    d_gent;   // greedy: (offset, tag) per seed of every R
 	uint32_t n_gpairs = 0;       // correcting: pairs whose R index is built in memory
 	// onepass member mode (dg_members.hip): member arrays share the record
 	// slots' indexing; the verification work queue
@@ -481,6 +483,7 @@ struct dg_encode_plan {
 };
 
 static const char* kStageNames[] = {"crc64", "diff", "scan", "serialize+join", "total", "members", "corr_build", "corr_scan"};
+static const char* kGreedyStageNames[] = {"greedy_build", "greedy_scan"};   // stages 6, 7 of a greedy plan
 
 // ── --verbose: the reference's diagnostics from device counters and the delta ──
 
@@ -569,6 +572,13 @@ void dg::print_verbose(const dg_encode_plan_t* P, uint32_t i, const uint64_t* st
 		print_command_stats(cmds);
 		return;
 	}
+	if (P->algo == DG_ALGO_GREEDY) {   // greedy.c:146-150, 255-257
+		fprintf(stderr, "greedy: %s, |R|=%llu, |V|=%llu, seed_len=%llu\n",
+		        ((P->opts.flags >> DG_OPT_SPLAY) & 1) ? "splay tree" : "hash table", (unsigned long long)d.r_len,
+		        (unsigned long long)d.v_len, (unsigned long long)p);
+		print_command_stats(cmds);
+		return;
+	}
 	// correcting.c:137-152, 200-214, 470-485
 	const uint64_t seeds = d.r_len >= p ? d.r_len - p + 1 : 0;
 	const uint64_t cap = x.q, m = x.m, k = st ? st[6] : 0;
@@ -631,11 +641,11 @@ int dg_encode_plan_create(dg_context_t* ctx, dg_algorithm_t algo, const dg_pair_
 	if (!ctx) return DG_ERR_INVALID_ARG;
 	dg_diff_options_t o;
 	if (opts) o = *opts; else dg_diff_options_default(&o);
-	if (algo == DG_ALGO_GREEDY)
-		return set_err(ctx, DG_ERR_UNSUPPORTED, "greedy is not implemented on the GPU path");
-	if (algo != DG_ALGO_ONEPASS && algo != DG_ALGO_CORRECTING)
+	if (algo != DG_ALGO_GREEDY && algo != DG_ALGO_ONEPASS && algo != DG_ALGO_CORRECTING)
 		return set_err(ctx, DG_ERR_INVALID_ARG, "unknown algorithm %d", (int)algo);
-	if ((o.flags >> DG_OPT_SPLAY) & 1)
+	// greedy: --splay only picks the smallest offset among the longest matches
+	// (greedy.c:174-195); for the other two it changes which seeds are kept
+	if (((o.flags >> DG_OPT_SPLAY) & 1) && algo != DG_ALGO_GREEDY)
 		return set_err(ctx, DG_ERR_UNSUPPORTED, "--splay is not supported (hash-table path only)");
 	if ((o.flags >> DG_OPT_INPLACE) & 1)
 		return set_err(ctx, DG_ERR_UNSUPPORTED,
@@ -657,7 +667,7 @@ int dg_encode_plan_create(dg_context_t* ctx, dg_algorithm_t algo, const dg_pair_
 	hipSetDevice(ctx->device);
 
 	std::map<uint64_t, uint64_t> qcache;
-	uint64_t rec = 0, bound = 0, ctab = 0;
+	uint64_t rec = 0, bound = 0, ctab = 0, gents = 0;
 	const uint64_t p = o.p;
 	for (uint32_t i = 0; i < n; ++i) {
 		const dg_pair_t& d = pairs[i];
@@ -675,6 +685,18 @@ int dg_encode_plan_create(dg_context_t* ctx, dg_algorithm_t algo, const dg_pair_
 			const uint64_t want = std::max<uint64_t>(o.q, seeds / p);   // onepass.c:61-62
 			auto it = qcache.find(want);
 			x.q = it != qcache.end() ? it->second : (qcache[want] = next_prime(want));
+		} else if (algo == DG_ALGO_GREEDY) {
+			// the seed index (dg_greedy.hip): a power-of-two bucket count >= the
+			// seed count, heads[buckets + 1] and one entry per seed;
+			// --table-size and --max-table do not apply (q stays 0)
+			uint64_t nb = 1;
+			while (nb < seeds) nb <<= 1;
+			x.f_size = nb;
+			x.tab_base = ctab;
+			x.m = gents;
+			ctab += nb + 1;
+			gents += seeds;
+			P->max_seeds = std::max<uint64_t>(P->max_seeds, seeds);
 		} else {
 			// correcting.c:116-129
 			const uint64_t mt = o.max_table > 0 ? o.max_table : DG_MAX_TABLE_SIZE;
@@ -694,7 +716,7 @@ int dg_encode_plan_create(dg_context_t* ctx, dg_algorithm_t algo, const dg_pair_
 			delete P;
 			return set_err(ctx, DG_ERR_TOO_LARGE, "table size %llu too large", (unsigned long long)x.q);
 		}
-		x.q_magic = UINT64_MAX / x.q;
+		x.q_magic = x.q ? UINT64_MAX / x.q : 0;
 		x.rec_base = rec;
 		x.rec_cap = (uint32_t)(d.v_len / p + 1);
 		rec += x.rec_cap;
@@ -702,7 +724,8 @@ int dg_encode_plan_create(dg_context_t* ctx, dg_algorithm_t algo, const dg_pair_
 		//   delta <= 35 + |V| + (|V|/p) * max(0, 22 - p);
 		// correcting: a tail-corrected COPY may be shorter than p, but there
 		// are at most |V|/p + 1 of them, each with at most one ADD header
-		if (algo == DG_ALGO_ONEPASS)
+		// (greedy: as onepass)
+		if (algo != DG_ALGO_CORRECTING)
 			bound += 35 + d.v_len + (d.v_len / p) * (p < 22 ? 22 - p : 0);
 		else
 			bound += 57 + d.v_len + 22 * (d.v_len / p);
@@ -712,7 +735,14 @@ int dg_encode_plan_create(dg_context_t* ctx, dg_algorithm_t algo, const dg_pair_
 	P->out_bound = bound;
 	P->total_rec = rec;
 	P->ctab_entries = ctab;
-	if (ctab * 4 > (64ull << 30)) {
+	if (algo == DG_ALGO_GREEDY) {
+		P->greedy_heads = ctab;
+		if (ctab * 4 + gents * 8 > (64ull << 30)) {
+			delete P;
+			return set_err(ctx, DG_ERR_NOMEM, "greedy seed indexes need %llu GiB (limit 64)",
+			               (unsigned long long)((ctab * 4 + gents * 8) >> 30));
+		}
+	} else if (ctab * 4 > (64ull << 30)) {
 		delete P;
 		return set_err(ctx, DG_ERR_NOMEM, "correcting R indexes need %llu GiB (limit 64)",
 		               (unsigned long long)(ctab >> 28));
@@ -830,7 +860,7 @@ int dg_encode_plan_create(dg_context_t* ctx, dg_algorithm_t algo, const dg_pair_
 	bad |= P->d_pairs.alloc(sizeof(PairDev) * std::max<uint32_t>(n, 1));
 	bad |= P->d_pplan.alloc(sizeof(PairPlanDev) * std::max<uint32_t>(n, 1));
 	bad |= P->d_powc.alloc(8 * p);
-	bad |= P->d_rec.alloc(4ull * (algo == DG_ALGO_ONEPASS ? kRecWordsOnepass : kRecWordsCorrecting) *
+	bad |= P->d_rec.alloc(4ull * (algo != DG_ALGO_CORRECTING ? kRecWordsOnepass : kRecWordsCorrecting) *
 	                      std::max<uint64_t>(rec, 1));
 	bad |= P->d_nrec.alloc(4ull * std::max<uint32_t>(n, 1));
 	bad |= P->d_dsize.alloc(8ull * std::max<uint32_t>(n, 1));
@@ -860,6 +890,10 @@ int dg_encode_plan_create(dg_context_t* ctx, dg_algorithm_t algo, const dg_pair_
 		const char* fz = ab_env("DG_FUSED");
 		P->fused = algo == DG_ALGO_ONEPASS && o.p == 16 && P->aligned16 && onepass16_selected() &&
 		           fz && fz[0] == '1';
+	}
+	if (algo == DG_ALGO_GREEDY) {
+		bad |= P->d_ctab.alloc(4ull * std::max<uint64_t>(ctab, 1));
+		bad |= P->d_gent.alloc(8ull * std::max<uint64_t>(gents, 1));
 	}
 	if (P->fused) bad |= P->d_lookback.alloc(8ull * std::max<uint32_t>(n, 1));
 	{
@@ -1027,7 +1061,7 @@ constexpr uint32_t kTimingAll = (1u << kTimingEvents) - 1u;
 static uint32_t timing_mask(const dg_encode_plan_t* P) {
 	if (P->timing_mode != DG_TIMING_DOMINANT) return kTimingAll;
 	if (P->members) return (1u << 2) | (1u << 6) | (1u << 3);   // the member kernel, then the chains
-	if (P->algo == DG_ALGO_CORRECTING) return (1u << 2) | (1u << 7) | (1u << 3);
+	if (P->algo != DG_ALGO_ONEPASS) return (1u << 2) | (1u << 7) | (1u << 3);   // build, scan
 	return (1u << 2) | (1u << 3);
 }
 
@@ -1061,7 +1095,8 @@ int dg_encode_plan_set_timing(dg_encode_plan_t* P, int slots) {
 // differencing kernel(s), 4 after the scan, 5 after serialisation + the CRC
 // join + the header patch (DG_FUSED=1: the join falls before 4), 6 after
 // the member kernel (member mode; else with 2), 7 after the correcting R-index build (before the V scan; onepass: with 3).  Stages
-// corr_build (2..7) and corr_scan (7..3) are reported for correcting plans only.
+// corr_build (2..7) and corr_scan (7..3) are reported for correcting plans only
+// (greedy plans: the same two intervals as greedy_build and greedy_scan).
 // Returns the mean over the runs recorded since set_timing (at most `slots`).
 int dg_encode_plan_stage_times(dg_encode_plan_t* P, float* ms, const char** names, int n) {
 	if (!P || !P->slots || !P->runs) return 0;
@@ -1070,7 +1105,7 @@ int dg_encode_plan_stage_times(dg_encode_plan_t* P, float* ms, const char** name
 	const uint32_t mask = timing_mask(P);
 	int sel[8], ns = 0;   // the stages whose two events were recorded
 	for (int k = 0; k < 8; ++k) {
-		if (k >= 6 && P->algo != DG_ALGO_CORRECTING) continue;
+		if (k >= 6 && P->algo == DG_ALGO_ONEPASS) continue;
 		if (k == 5 && P->members == false && mask != kTimingAll) continue;
 		if ((mask >> pairs[k][0] & 1) && (mask >> pairs[k][1] & 1)) sel[ns++] = k;
 	}
@@ -1088,7 +1123,7 @@ int dg_encode_plan_stage_times(dg_encode_plan_t* P, float* ms, const char** name
 	int i = 0;
 	for (; i < ns && i < n; ++i) {
 		if (ms) ms[i] = (float)(acc[i] / used);
-		if (names) names[i] = kStageNames[sel[i]];
+		if (names) names[i] = sel[i] >= 6 && P->algo == DG_ALGO_GREEDY ? kGreedyStageNames[sel[i] - 6] : kStageNames[sel[i]];
 	}
 	return i;
 }
@@ -1294,6 +1329,25 @@ int dg_encode_plan_run(dg_encode_plan_t* P, const uint8_t* d_ref, const uint8_t*
 				}
 				HIPCHK(ctx, launch_onepass(a, a.p, P->aligned16, st));
 			}
+		} else if (P->algo == DG_ALGO_GREEDY) {
+			// zeroed bucket counts, the seed index of every R, then the V scan
+			GreedyArgs g{};
+			g.ref = d_ref;
+			g.ver = d_ver;
+			g.pairs = a.pairs;
+			g.pplan = a.pplan;
+			g.n_pairs = P->n;
+			g.p = a.p;
+			g.splay = (uint32_t)((P->opts.flags >> DG_OPT_SPLAY) & 1);
+			g.max_seeds = (uint32_t)P->max_seeds;
+			g.heads = P->d_ctab.as<uint32_t>();
+			g.ent = P->d_gent.as<uint2>();
+			g.rec = a.rec;
+			g.n_rec = a.n_rec;
+			g.dsize = a.dsize;
+			g.status = d_status;
+			HIPCHK(ctx, launch_greedy(g, P->greedy_heads, st,
+			                          timed && (timing_mask(P) & (1u << 7)) ? P->cur[7] : nullptr));
 		} else {
 			// fresh R indexes (~0 = empty slot), then build + scan
 			a.ctab = P->d_ctab.as<uint32_t>();
@@ -1313,7 +1367,7 @@ int dg_encode_plan_run(dg_encode_plan_t* P, const uint8_t* d_ref, const uint8_t*
 			                              timed && (timing_mask(P) & (1u << 7)) ? P->cur[7] : nullptr,
 			                              (P->crc_fused || P->crc_wide_beside) && !serial ? P->ev_fork : nullptr));
 		}
-		if (P->algo != DG_ALGO_CORRECTING) HIPCHK(ctx, rec(7, st));
+		if (P->algo == DG_ALGO_ONEPASS) HIPCHK(ctx, rec(7, st));
 		HIPCHK(ctx, rec(3, st));
 		return DG_OK;
 	};
@@ -1359,7 +1413,7 @@ int dg_encode_plan_run(dg_encode_plan_t* P, const uint8_t* d_ref, const uint8_t*
 	s.pairs = P->d_pairs.as<PairDev>();
 	s.pplan = P->d_pplan.as<PairPlanDev>();
 	s.rec = P->d_rec.as<uint32_t>();
-	s.rec_words = P->algo == DG_ALGO_ONEPASS ? kRecWordsOnepass : kRecWordsCorrecting;
+	s.rec_words = P->algo != DG_ALGO_CORRECTING ? kRecWordsOnepass : kRecWordsCorrecting;
 	s.n_rec = P->d_nrec.as<uint32_t>();
 	s.crc = P->d_crc.as<uint64_t>();
 	s.offsets = d_offsets;

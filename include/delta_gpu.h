@@ -7,9 +7,10 @@
  *   ---------------------------------------------   ---------------------------
  *   delta_crc64_xz(R), delta_crc64_xz(V)            \
  *     (src/c/delta.h:294-322)                        \
- *   delta_diff(ALGO_ONEPASS|ALGO_CORRECTING, ...)     > dg_encode / dg_encode_batch /
- *     (src/c/correcting.c:499-519 -> onepass.c:32,   /  dg_encode_plan_run
- *      correcting.c:81)                             /
+ *   delta_diff(ALGO_GREEDY|ALGO_ONEPASS|              > dg_encode / dg_encode_batch /
+ *     ALGO_CORRECTING, ...)                          /  dg_encode_plan_run
+ *     (src/c/correcting.c:499-519 -> greedy.c:88,   /
+ *      onepass.c:32, correcting.c:81)              /
  *   delta_place_commands (src/c/apply.c:136-164)   /
  *   delta_encode(placed, false, |V|, src, dst)    /
  *     (src/c/encoding.c:39-90)
@@ -27,9 +28,19 @@
  *     (delta.h:44-79, encoding.c:119-172);
  *   - no per-command allocations: results are arenas with explicit frees;
  *   - thread-safe: constant tables are built at context creation;
- *   - DELTA_OPT_SPLAY (delta.h:222) and ALGO_GREEDY are rejected with
- *     DG_ERR_UNSUPPORTED (splay changes correcting output; greedy is outside
- *     the GPU hot path);
+ *   - DELTA_OPT_SPLAY (delta.h:222) is accepted for ALGO_GREEDY only, where
+ *     it selects the smallest instead of the largest offset among the longest
+ *     matches (its only effect on greedy's output, greedy.c:174-216); with
+ *     onepass or correcting it is rejected with DG_ERR_UNSUPPORTED (splay
+ *     changes their output);
+ *   - greedy ignores q, max_table and buf_cap (as the reference's greedy
+ *     does: its output does not depend on its hash table).  Each pair's R is
+ *     indexed whole on the device: 4 (B + 1) + 8 S bytes for S = |R| - p + 1
+ *     seeds and B = S rounded up to a power of two, at most 64 GiB per plan
+ *     (DG_ERR_NOMEM above that).  Like the reference's, its time is quadratic
+ *     on self-similar data (every equal seed is a candidate, each extended
+ *     to its end: a long run of one byte, a short period): one such pair
+ *     holds its wave for as long, while the rest of the batch proceeds;
  *   - inputs of 4 GiB or more are rejected (DG_ERR_TOO_LARGE): the format's
  *     u32 fields would silently truncate them (encoding.c:63,72-78).
  *
@@ -60,7 +71,7 @@ extern "C" {
 typedef enum {
 	DG_OK              = 0,
 	DG_ERR_INVALID_ARG = 1,
-	DG_ERR_UNSUPPORTED = 2,   /* greedy, --splay, --inplace encode */
+	DG_ERR_UNSUPPORTED = 2,   /* --splay with onepass or correcting, --inplace on a plan */
 	DG_ERR_TOO_LARGE   = 3,   /* a buffer >= 4 GiB */
 	DG_ERR_NO_DEVICE   = 4,
 	DG_ERR_HIP         = 5,
@@ -180,7 +191,7 @@ int dg_encode_plan_create(dg_context_t *ctx, dg_algorithm_t algo,
 uint64_t dg_encode_plan_output_bound(const dg_encode_plan_t *plan);
 uint32_t dg_encode_plan_num_pairs(const dg_encode_plan_t *plan);
 /* Table size q actually used for pair i (onepass.c:61-62 /
- * correcting.c:116-123 sizing). */
+ * correcting.c:116-123 sizing); 0 for a greedy plan, which has none. */
 uint64_t dg_encode_plan_table_size(const dg_encode_plan_t *plan, uint32_t i);
 int dg_encode_plan_run(dg_encode_plan_t *plan,
                        const uint8_t *d_ref_arena, const uint8_t *d_ver_arena,
@@ -197,10 +208,12 @@ int dg_encode_plan_run(dg_encode_plan_t *plan,
  * "members" is the member kernel alone, inside "diff", 0 in plain chain mode).  Returns
  * the number of stages.  No host synchronisation happens until stage_times.
  * Correcting plans add "corr_build" and "corr_scan" (the R-index build and
- * the V scan).  dg_encode_plan_set_timing_mode(plan, DG_TIMING_DOMINANT)
+ * the V scan), greedy plans "greedy_build" and "greedy_scan" (the seed index
+ * of every R and the V scan).  dg_encode_plan_set_timing_mode(plan, DG_TIMING_DOMINANT)
  * records only the events around the dominant kernel(s) — the member kernel
- * ("members"), the correcting build and scan ("corr_build", "corr_scan",
- * "diff") or the onepass kernel ("diff") — and stage_times reports those
+ * ("members"), the correcting or greedy build and scan ("corr_build",
+ * "corr_scan" or "greedy_build", "greedy_scan", and "diff") or the onepass
+ * kernel ("diff") — and stage_times reports those
  * only: each timing event costs the run stream a few microseconds, so a
  * throughput measurement records as few as it needs.
  * dg_encode_plan_set_timing_every(plan, k), k >= 1: only every k-th run
@@ -422,7 +435,8 @@ void dg_commands_free(dg_commands_t *cmds);
 /* delta_diff(algo, R, V, opts) followed by delta_place_commands (apply.c:
  * 136-164): the commands of the delta dg_encode produces, in algorithm order
  * with sequential dst (so dropping dst gives delta_diff's list).  Runs on the
- * GPU; DG_OPT_INPLACE in opts->flags is ignored (in-place conversion is
+ * GPU for all three algorithms (DG_OPT_SPLAY: greedy only, see above);
+ * DG_OPT_INPLACE in opts->flags is ignored (in-place conversion is
  * dg_make_inplace on an encoded delta). */
 int dg_diff(dg_context_t *ctx, dg_algorithm_t algo,
             const uint8_t *r, size_t r_len, const uint8_t *v, size_t v_len,
