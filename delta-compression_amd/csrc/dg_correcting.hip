@@ -87,24 +87,6 @@ __device__ __forceinline__ uint64_t roll61w(uint64_t fp, uint64_t nb, uint32_t i
 	return ((uint64_t)rh << 32) | rl;
 }
 
-// roll61w with the leaving byte's term computed instead of looked up: x *
-// cneg == -x 263^p (mod M) for cneg = M - 263^p mod M, split into its dwords
-// (x cneg_lo < 2^40, x cneg_hi < 2^37), so P < 2^41 and Q < 2^39 and the same
-// fold applies.  Two more multiply-adds per step, and no LDS read (with its
-// wait, which also waited for the slot atomics issued before it) on the
-// rolling chain.
-__device__ __forceinline__ uint64_t roll61x(uint64_t fp, uint32_t x, uint32_t cneg_lo, uint32_t cneg_hi, uint32_t in) {
-	const uint64_t P = (uint64_t)(uint32_t)fp * (uint32_t)kBase + (uint64_t)x * cneg_lo;
-	const uint64_t Q = (uint64_t)(uint32_t)(fp >> 32) * (uint32_t)kBase + (uint64_t)x * cneg_hi;
-	const uint32_t s = (uint32_t)(Q >> 29) + in;
-	const uint32_t tl = (uint32_t)P + s;
-	const uint32_t th = (uint32_t)(P >> 32) + ((uint32_t)Q & 0x1FFFFFFFu) + (tl < s ? 1u : 0u);
-	const uint32_t f = th >> 29;
-	const uint32_t rl = tl + f;
-	const uint32_t rh = (th & 0x1FFFFFFFu) + (rl < f ? 1u : 0u);
-	return ((uint64_t)rh << 32) | rl;
-}
-
 // r <= M + 2 to [0, M): r - M = r + 1 - 2^61 leaves only the low dword + 1
 __device__ __forceinline__ uint64_t fp61_canon(uint64_t r) {
 	const bool ge = r >= kMersenne;
@@ -262,13 +244,7 @@ __device__ uint32_t ext_from(const uint8_t* a, const uint8_t* b, uint32_t ml, ui
 // backward a[-1], a[-2], ... vs b[-1], ... up to blim; their first steps
 // (kFwdFirst / kBwdFirst KiB) together, loaded with the seed verify of the
 // candidates (correcting_scan_kernel), the rest in 4 KiB steps
-#ifndef DG_EXT_FWD_FIRST
-#define DG_EXT_FWD_FIRST 1
-#endif
-#ifndef DG_EXT_BWD_FIRST
-#define DG_EXT_BWD_FIRST 1
-#endif
-constexpr int kFwdFirst = DG_EXT_FWD_FIRST, kBwdFirst = DG_EXT_BWD_FIRST;
+constexpr int kFwdFirst = 1, kBwdFirst = 1;
 struct ExtPair {
 	ExtStep<kFwdFirst> f;
 	ExtStep<kBwdFirst> b;
@@ -419,14 +395,6 @@ __global__ __launch_bounds__(kBuildBlock) void correcting_build_kernel(EncodeArg
 // raw CRC of R followed by pad = 32 Ki * iterations - |R| zero bytes; the
 // plan's per-pair x^(-8 pad) removes them.  init = ~0 is the first 8 bytes
 // XOR-ed with 0xFF (lane 0, iteration 0), xorout the final inversion.
-#ifndef DG_CORR_CHAINS   // rolling chains per lane in the LDS build (2 or 4)
-#define DG_CORR_CHAINS 2
-#endif
-constexpr uint32_t kCorrChains = DG_CORR_CHAINS;
-static_assert(kCorrChains == 2 || kCorrChains == 4, "chains per lane");
-#ifndef DG_CORR_NB_LDS   // 0 (A/B): the leaving byte's term computed (roll61x), measured 1-2 % slower
-#define DG_CORR_NB_LDS 1
-#endif
 constexpr uint32_t kBuildLdsBlock = 1024;
 constexpr uint32_t kCrcPiece = kBuildSeedsPerLane;                    // bytes per lane per iteration
 constexpr uint32_t kCrcStride = kBuildLdsBlock * kBuildSeedsPerLane;  // 32 KiB per iteration
@@ -446,12 +414,6 @@ __global__ __launch_bounds__(kBuildLdsBlock) void correcting_build_lds_kernel(En
 	uint32_t* H = a.ctab + pp.tab_base;
 	for (uint32_t i = tid; i < cap; i += kBuildLdsBlock) T[i] = kNone;
 	if (tid < 256) nb[tid] = roll_table(tid, a.powc[0]);
-	// -263^p mod M as dwords (roll61x); uniform
-	[[maybe_unused]] const uint64_t cneg = [&] {
-		const uint64_t v = mulsmall61(a.powc[0], (uint32_t)kBase);
-		return v ? kMersenne - v : 0ull;
-	}();
-	[[maybe_unused]] const uint32_t cneg_lo = (uint32_t)cneg, cneg_hi = (uint32_t)(cneg >> 32);
 	if constexpr (CRC) {
 		for (uint32_t i = tid; i < 4 * 256; i += kBuildLdsBlock) CT[i] = a.crc_tab[i];
 		if (tid < 256) CT[4 * 256 + tid] = a.crc_tab[8 * 256 + 5 * kCrcNibTabWords + tid];   // level 5: x^(8*32 Ki)
@@ -522,41 +484,14 @@ __global__ __launch_bounds__(kBuildLdsBlock) void correcting_build_lds_kernel(En
 						w[11] >>= 8;
 					}
 					auto byte_at = [&](uint32_t i) -> uint32_t { return (w[i >> 2] >> (8 * (i & 3))) & 0xFFu; };
-					if constexpr (kCorrChains == 4) {
-						// four independent rolling chains (seeds 0..7, 8..15,
-						// 16..23, 24..31): two more direct fingerprints per piece,
-						// half the dependent rolls per chain
-						uint64_t f[4];
-#pragma unroll
-						for (uint32_t c = 0; c < 4; ++c) f[c] = fp16_dot(w[2 * c], w[2 * c + 1], w[2 * c + 2], w[2 * c + 3]);
-#pragma unroll
-						for (uint32_t j = 0; j < kBuildSeedsPerLane / 4; ++j) {
-							if (j) {
-#pragma unroll
-								for (uint32_t c = 0; c < 4; ++c)
-									f[c] = roll61w(f[c], nb[byte_at(8 * c + j - 1)], byte_at(8 * c + j + 15));
-							}
-							if (__ballot(f[0] >= kMersenne || f[1] >= kMersenne || f[2] >= kMersenne || f[3] >= kMersenne)) {
-#pragma unroll
-								for (uint32_t c = 0; c < 4; ++c) f[c] = fp61_canon(f[c]);
-							}
-#pragma unroll
-							for (uint32_t c = 0; c < 4; ++c) insert(f[c], (uint32_t)(s0 + 8 * c + j));
-						}
-					} else {
 					// two independent rolling chains (seeds 0..15 and 16..31)
 					uint64_t fa = fp16_dot(w[0], w[1], w[2], w[3]);
 					uint64_t fb = fp16_dot(w[4], w[5], w[6], w[7]);
 #pragma unroll
 					for (uint32_t j = 0; j < kBuildSeedsPerLane / 2; ++j) {
 						if (j) {   // roll (hash.c:62-98), weakly reduced
-#if DG_CORR_NB_LDS
 							fa = roll61w(fa, nb[byte_at(j - 1)], byte_at(j + 15));
 							fb = roll61w(fb, nb[byte_at(j + 15)], byte_at(j + 31));
-#else
-							fa = roll61x(fa, byte_at(j - 1), cneg_lo, cneg_hi, byte_at(j + 15));
-							fb = roll61x(fb, byte_at(j + 15), cneg_lo, cneg_hi, byte_at(j + 31));
-#endif
 						}
 						// a weakly reduced value >= M is ~2^-60 likely: one
 						// compare per seed, the subtract only in a wave that has one
@@ -566,7 +501,6 @@ __global__ __launch_bounds__(kBuildLdsBlock) void correcting_build_lds_kernel(En
 						}
 						insert(fa, (uint32_t)(s0 + j));
 						insert(fb, (uint32_t)(s0 + 16 + j));
-					}
 					}
 				} else if (cnt) {
 					uint64_t fp = window_fp<0>(R + s0, p, a.powc);

@@ -123,7 +123,6 @@ struct EncodeArgs {
 	uint64_t* kcls;            // per pair: checkpoint class k (correcting.c:131-136), computed once
 	const uint32_t* gpairs;    // the pairs whose R index is built in memory (q > the LDS capacity)
 	uint32_t n_gpairs;
-	uint32_t dbg;              // A/B switches (DG_DEBUG_BITS, A/B builds only), 0 in the product
 	// member mode (onepass16_kernel after the member kernels, dg_members.hip):
 	// verified diagonal members are taken as they are; nullptr = plain chain
 	const uint32_t* mem_s;     // per member slot (PairPlanDev::mem_base + chunk slots): epoch start
@@ -235,13 +234,12 @@ struct SerArgs {
 	const uint32_t* rec;
 	uint32_t rec_words;        // 3 or 4 (kRecWords*)
 	const uint32_t* n_rec;
-	const uint64_t* crc;       // 2 per pair: R, V
+	const uint64_t* crc;       // 2 per pair: R, V (final: the kernel writes header bytes 9..24)
 	const uint64_t* offsets;   // n+1
 	uint8_t* out;
 	uint64_t out_cap;
 	int32_t* status;
 	uint32_t n_pairs;
-	uint32_t crc_in;           // the CRCs are final: write header bytes 9..24 here (no crc_patch_kernel)
 };
 
 struct CrcArgs {
@@ -272,7 +270,6 @@ struct DecodeArgs {
 	uint8_t* out;
 	uint64_t* out_len;
 	int32_t* status;
-	uint32_t dbg;              // A/B switches (DG_DEBUG_BITS, A/B builds only), 0 in the product
 	const uint64_t* tables;    // CRC tables (CrcArgs::tables); with crc_check
 	uint32_t crc_check;        // 1: src/dst CRC-64/XZ computed and checked in-kernel (main.c:341-385)
 };
@@ -318,7 +315,7 @@ hipError_t launch_greedy(const GreedyArgs& g, uint64_t head_words, hipStream_t s
 // (route_cnt / route_fb: the routed-pair count moved to a host-mapped word)
 hipError_t launch_scan(const uint64_t* sz, uint64_t* off, uint32_t n, hipStream_t st,
                        uint32_t* route_cnt = nullptr, uint32_t* route_fb = nullptr);
-hipError_t launch_serialize_wave(const SerArgs& s, hipStream_t st);   // wave per pair, CRCs patched after
+hipError_t launch_serialize_wave(const SerArgs& s, hipStream_t st);   // wave per pair, header CRCs included
 hipError_t launch_crc_patch(uint8_t* out, const uint64_t* offsets, const uint64_t* crc,
                             const int32_t* status, uint32_t n, hipStream_t st);
 // pass: the row-interleaved pass on byte tables (16 KiB LDS per block) or on

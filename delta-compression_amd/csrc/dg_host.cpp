@@ -447,17 +447,10 @@ struct dg_encode_plan {
 	// fork/join of the CRC kernels onto a side stream
 	hipStream_t side = nullptr;
 	hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-	bool serial_crc = false;   // DG_SERIAL_CRC=1: CRC on the run stream (A/B)
-	bool crc_first = false;    // DG_CRC_FIRST=1: enqueue the CRC before the differencing (A/B)
-	bool chain_join = false;   // DG_CHAIN_JOIN=1: member plans' routed chain always waits for the CRC pass (A/B)
-	bool crc_late_fin = true;  // member plans: the CRC's combine after the chains (DG_CRC_JOIN=0: not, A/B)
-	bool crc_patch = false;    // DG_CRC_PATCH=1: header CRCs by crc_patch_kernel after the serialiser (A/B)
+	bool serial_crc = false;   // DG_SERIAL_CRC=1: CRC on the run stream, before the differencing (A/B bound)
 	bool skip_crc = false;     // DG_SKIP_CRC=1: no CRC kernels, wrong header CRCs (A/B bound only)
 	uint32_t corr_lds_cap = 0; // correcting: R indexes up to this many slots built in LDS (DG_CORR_BUILD=global: none)
 	bool crc_fused = false;    // correcting: R's CRC computed by the LDS build, V's forked after it
-	bool op_crc = false;       // onepass plain plans: both CRCs computed by the onepass waves (no CRC pass)
-	bool crc_wide = false;     // correcting: R's and V's CRC in one wide-table pass before the build
-	bool crc_wide_beside = false;   // ... or forked after the build, beside the V scan
 	uint32_t route_min = 0;    // member mode chosen automatically: route poorly verified pairs to the plain chain
 	// automatic member mode: the routed-pair count of the last completed run
 	// (written by scan_sizes_kernel into mapped host memory) decides whether the
@@ -469,7 +462,6 @@ struct dg_encode_plan {
 	uint64_t* stats = nullptr; // dg_encode_plan_set_stats: --verbose counters (device, 8 per pair)
 	uint64_t qmin = ~0ull;
 	uint64_t v_total = 0;      // sum |V| of the batch
-	uint32_t dbg = 0;          // DG_DEBUG_BITS: kernel A/B switches (A/B builds only)
 	bool fused = false;        // DG_FUSED=1: onepass16 serialises in-kernel (default: scan + serialise)
 	// timing
 	bool timing = false;
@@ -630,10 +622,6 @@ static bool members_wanted(const dg_context_t* ctx, const dg_pair_t* pairs, uint
 #define DG_CRC_PRIO_FLAG 0
 #endif
 constexpr bool kCrcPrioFlag = DG_CRC_PRIO_FLAG != 0;
-#ifndef DG_OP_CRC_DEFAULT   // 1 (A/B): onepass plain plans compute their CRCs in the onepass waves
-#define DG_OP_CRC_DEFAULT 0   // (measured slower: C2 1786 -> 1172 GiB/s, profiles/r06_experiments.md)
-#endif
-constexpr bool kOpCrcDefault = DG_OP_CRC_DEFAULT != 0;
 
 int dg_encode_plan_create(dg_context_t* ctx, dg_algorithm_t algo, const dg_pair_t* pairs,
                           uint32_t n, const dg_diff_options_t* opts, dg_encode_plan_t** out) {
@@ -762,33 +750,20 @@ int dg_encode_plan_create(dg_context_t* ctx, dg_algorithm_t algo, const dg_pair_
 		int shm = 0;
 		if (hipDeviceGetAttribute(&shm, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device) != hipSuccess)
 			shm = 0;
-		// Correcting plans compute the CRCs in one of four ways (A/B:
-		// DG_CORR_CRC = fused | wide | widebeside | beside):
-		//   fused  (default) the LDS build computes R's CRC from the bytes it
-		//          holds and V's runs beside the V scan (C4: 2.77 ms per step);
-		//   wide   one pass over R and V before the build, with the GPU to
-		//          itself: bank-spread slicing tables in 128 KiB of LDS per CU
-		//          (crc_segments_wide_kernel), ~2 LDS cycles a lookup (2.84 ms);
-		//   widebeside  the wide pass forked after the build, beside the V
-		//          scan (2.80 ms: it outlasts the scan);
-		//   beside the onepass arrangement: both CRCs on the side stream
-		//          beside the build (whose 130 KiB-LDS blocks leave it ~1/8 of
-		//          each CU).
-		const char* cm = ab_env("DG_CORR_CRC");
-		int mode = 1;
-		if (cm) mode = !strcmp(cm, "wide") ? 2 : (!strcmp(cm, "beside") ? 0 : (!strcmp(cm, "widebeside") ? 3 : 1));
-		if (algo != DG_ALGO_CORRECTING || !n) mode = 0;
-		if ((mode == 2 || mode == 3) && shm < 8 * 4 * 256 * 16 + 1024) mode = 0;
-		// one block's LDS less the 2 KiB roll table, the fused R CRC's tables
+		// Correcting plans compute the CRCs in one of two ways:
+		//   fused   where some R index fits LDS: the LDS build computes R's CRC
+		//           from the bytes it holds and V's runs beside the V scan (C4:
+		//           2.77 ms per step);
+		//   beside  otherwise, the onepass arrangement: both CRCs on the side
+		//           stream beside the build.
+		// One block's LDS less the 2 KiB roll table, the fused R CRC's tables
 		// (10 KiB) and reduction words, and some slack
-		const int fixed = 2048 + (mode == 1 ? 10240 + 128 : 0) + 256;
+		const int fixed = 2048 + 10240 + 128 + 256;
 		if (algo == DG_ALGO_CORRECTING && !(cb && strcmp(cb, "global") == 0) && shm > fixed + 4096)
 			P->corr_lds_cap = (uint32_t)((shm - fixed) / 4);
 		// fused: only R indexes built in LDS compute R's CRC; the others' R
 		// CRCs run in V's pass
-		P->crc_fused = mode == 1 && P->corr_lds_cap && P->qmin <= P->corr_lds_cap;
-		P->crc_wide = mode == 2 || mode == 3;
-		P->crc_wide_beside = mode == 3;
+		P->crc_fused = P->corr_lds_cap && P->qmin <= P->corr_lds_cap;
 	}
 	if (P->crc_fused) {   // x^(-8 pad) of each R's zero padding to a multiple of 32 KiB
 		uint64_t xm8 = 1ULL << 63;
@@ -808,25 +783,11 @@ int dg_encode_plan_create(dg_context_t* ctx, dg_algorithm_t algo, const dg_pair_
 			P->pp[i].crc_unpad = it->second;
 		}
 	}
-	// onepass plain plans (the LDS-window chain, no member mode, no in-kernel
-	// serialisation) with DG_OP_CRC_DEFAULT=1: the onepass waves compute both
-	// CRCs from the bytes their windows stage (onepass16_crc_kernel), so no
-	// CRC pass reads R and V a second time.  Off in the product: the folds
-	// lengthen every wave's latency-bound chain (C2 kernel 0.221 -> 0.375 ms)
-	// by far more than the rows pass beside it costs the step (~0.02 ms).
-	// DG_OP_CRC=0 (A/B builds) turns it off in such a build.
-	{
-		const char* oc = ab_env("DG_OP_CRC");
-		const char* fz = ab_env("DG_FUSED");
-		P->op_crc = kOpCrcDefault && algo == DG_ALGO_ONEPASS && o.p == 16 && P->aligned16 && onepass16_selected() &&
-		            !(fz && fz[0] == '1') && !members_wanted(ctx, pairs, n) && !(oc && oc[0] == '0');
-	}
-	// CRC spans: 2 per pair (R then V; V only when the build computes R's;
-	// none when the onepass waves compute both); arena offsets are rebased at
-	// run time
+	// CRC spans: 2 per pair (R then V; V only when the build computes R's);
+	// arena offsets are rebased at run time
 	std::vector<dg_span_t> spans;
 	std::vector<uint32_t> which, outs;
-	for (uint32_t i = 0; i < n && !P->op_crc; ++i) {
+	for (uint32_t i = 0; i < n; ++i) {
 		if (!P->crc_fused || P->pp[i].q > P->corr_lds_cap) {
 			spans.push_back(dg_span_t{pairs[i].r_off, pairs[i].r_len});
 			which.push_back(0);
@@ -891,11 +852,11 @@ int dg_encode_plan_create(dg_context_t* ctx, dg_algorithm_t algo, const dg_pair_
 		P->fused = algo == DG_ALGO_ONEPASS && o.p == 16 && P->aligned16 && onepass16_selected() &&
 		           fz && fz[0] == '1';
 	}
+	if (P->fused) bad |= P->d_lookback.alloc(8ull * std::max<uint32_t>(n, 1));
 	if (algo == DG_ALGO_GREEDY) {
 		bad |= P->d_ctab.alloc(4ull * std::max<uint64_t>(ctab, 1));
 		bad |= P->d_gent.alloc(8ull * std::max<uint64_t>(gents, 1));
 	}
-	if (P->fused) bad |= P->d_lookback.alloc(8ull * std::max<uint32_t>(n, 1));
 	{
 		// member mode: p = 16 onepass over 16-byte aligned pairs (the LDS-window
 		// chain), i.e. the batched hot configuration; DG_NO_MEMBERS=1 (A/B
@@ -988,16 +949,6 @@ int dg_encode_plan_create(dg_context_t* ctx, dg_algorithm_t algo, const dg_pair_
 	}
 	const char* sc = ab_env("DG_SERIAL_CRC");
 	P->serial_crc = sc && sc[0] == '1';
-	const char* db = ab_env("DG_DEBUG_BITS");
-	P->dbg = db ? (uint32_t)strtoul(db, nullptr, 0) : 0;
-	const char* cf = ab_env("DG_CRC_FIRST");
-	P->crc_first = cf && cf[0] == '1';
-	const char* chj = ab_env("DG_CHAIN_JOIN");
-	P->chain_join = chj && chj[0] == '1';
-	const char* cj = ab_env("DG_CRC_JOIN");
-	if (cj) P->crc_late_fin = cj[0] != '0';
-	const char* cp = ab_env("DG_CRC_PATCH");
-	P->crc_patch = cp && cp[0] == '1';
 	const char* sk = ab_env("DG_SKIP_CRC");
 	P->skip_crc = sk && sk[0] == '1';
 
@@ -1093,8 +1044,9 @@ int dg_encode_plan_set_timing(dg_encode_plan_t* P, int slots) {
 
 // Per-run events: 0/1 around the CRC kernels (side stream), 2/3 around the
 // differencing kernel(s), 4 after the scan, 5 after serialisation + the CRC
-// join + the header patch (DG_FUSED=1: the join falls before 4), 6 after
-// the member kernel (member mode; else with 2), 7 after the correcting R-index build (before the V scan; onepass: with 3).  Stages
+// join + the header CRCs (member plans: crc_patch_kernel; DG_FUSED=1: the join
+// falls before 4), 6 after the member kernel (member mode; else with 2), 7
+// after the correcting R-index build (before the V scan; onepass: with 3).  Stages
 // corr_build (2..7) and corr_scan (7..3) are reported for correcting plans only
 // (greedy plans: the same two intervals as greedy_build and greedy_scan).
 // Returns the mean over the runs recorded since set_timing (at most `slots`).
@@ -1167,6 +1119,95 @@ static MemSerArgs mem_ser_args(const dg_encode_plan_t* P, const uint8_t* d_ver, 
 // run in this many runs in member mode (the others as a plain plan)
 constexpr uint32_t kProbeEvery = 16;
 
+// onepass: the plain chain; or (mem) the member kernel, ev_members (nullable,
+// stage timing), then the member chain and, for the pairs it routes, the plain
+// chain (after routed_after, when set)
+static int enqueue_onepass(dg_encode_plan_t* P, EncodeArgs a, bool mem, hipEvent_t ev_members,
+                           hipEvent_t routed_after, hipStream_t st) {
+	dg_context_t* ctx = P->ctx;
+	if (!mem) {
+		HIPCHK(ctx, launch_onepass(a, a.p, P->aligned16, st));
+		return DG_OK;
+	}
+	SpecArgs m{};
+	m.ref = a.ref;
+	m.ver = a.ver;
+	m.pairs = a.pairs;
+	m.pplan = a.pplan;
+	m.chunks = P->d_chunks.as<uint2>();
+	m.mem_s = P->d_mem_s.as<uint32_t>();
+	m.n_mem = P->d_nmem.as<uint32_t>();
+	m.srec = P->d_srec.as<uint32_t>();
+	m.csum = P->d_csum.as<uint32_t>();
+	m.cmap = P->d_cmap.as<uint32_t>();
+	a.csum = m.csum;
+	a.cmap = m.cmap;
+	a.seg = P->d_seg.as<uint32_t>();
+	a.nseg = P->d_nseg.as<uint32_t>();
+	a.route_min = P->route_min;
+	a.mem_s = m.mem_s;
+	a.n_mem = m.n_mem;
+	a.srec = m.srec;
+	HIPCHK(ctx, launch_members(m, P->n_chunks, ctx->n_cu, st));
+	if (kCrcPrioFlag) HIPCHK(ctx, hipMemsetD32Async(P->d_prio_flag.p, 1, 1, st));   // the rows pass to priority 1
+	if (ev_members) HIPCHK(ctx, hipEventRecord(ev_members, st));
+	if (P->route_min) a.route_cnt = P->d_route_cnt.as<uint32_t>();
+	HIPCHK(ctx, launch_onepass(a, a.p, P->aligned16, st, routed_after));
+	return DG_OK;
+}
+
+// greedy: zeroed bucket counts, the seed index of every R, then the V scan
+static int enqueue_greedy(dg_encode_plan_t* P, const EncodeArgs& a, hipEvent_t ev_built, hipStream_t st) {
+	GreedyArgs g{};
+	g.ref = a.ref;
+	g.ver = a.ver;
+	g.pairs = a.pairs;
+	g.pplan = a.pplan;
+	g.n_pairs = P->n;
+	g.p = a.p;
+	g.splay = (uint32_t)((P->opts.flags >> DG_OPT_SPLAY) & 1);
+	g.max_seeds = (uint32_t)P->max_seeds;
+	g.heads = P->d_ctab.as<uint32_t>();
+	g.ent = P->d_gent.as<uint2>();
+	g.rec = a.rec;
+	g.n_rec = a.n_rec;
+	g.dsize = a.dsize;
+	g.status = a.status;
+	HIPCHK(P->ctx, launch_greedy(g, P->greedy_heads, st, ev_built));
+	return DG_OK;
+}
+
+// correcting: fresh R indexes (~0 = empty slot), then build + scan; ev_fork
+// (nullable) is recorded after the build, where V's CRC forks
+static int enqueue_correcting(dg_encode_plan_t* P, EncodeArgs a, hipEvent_t ev_built, hipEvent_t ev_fork,
+                              hipStream_t st) {
+	dg_context_t* ctx = P->ctx;
+	a.buf_cap = (uint32_t)P->opts.buf_cap;
+	a.stats = P->stats;
+	a.ctab = P->d_ctab.as<uint32_t>();
+	a.kcls = P->d_kcls.as<uint64_t>();
+	a.max_seeds = (uint32_t)P->max_seeds;
+	// the LDS build writes every slot of every index; the global
+	// build only fills, so its tables start empty (~0)
+	a.gpairs = P->d_gpairs.as<uint32_t>();
+	a.n_gpairs = P->n_gpairs;
+	HIPCHK(ctx, launch_correcting_clear(a, st));
+	if (P->crc_fused) {
+		a.crc_out = P->d_crc.as<uint64_t>();
+		a.crc_tab = ctx->d_crc_tables;
+		a.crc_k32 = ctx->d_k32;
+	}
+	HIPCHK(ctx, launch_correcting(a, a.p, st, P->corr_lds_cap, P->qmin, ev_built, ev_fork));
+	return DG_OK;
+}
+
+// The run's stream graph:
+//   hints (from the last completed run) -> fork the side stream ->
+//   {differencing on the run stream, CRC pass on the side stream}, in one of
+//   two enqueue orders; or, for a fused correcting plan, differencing -> fork
+//   after the R-index build -> V's CRC beside the V scan ->
+//   scan of the delta sizes -> serialise (plain or member) with the join.
+// (DG_FUSED=1, A/B: join and header patch right after the differencing.)
 int dg_encode_plan_run(dg_encode_plan_t* P, const uint8_t* d_ref, const uint8_t* d_ver,
                        uint8_t* d_out, uint64_t out_cap, uint64_t* d_offsets, int32_t* d_status,
                        void* stream) {
@@ -1181,88 +1222,81 @@ int dg_encode_plan_run(dg_encode_plan_t* P, const uint8_t* d_ref, const uint8_t*
 
 	// The CRC-64/XZ of every R (even spans) and V (odd spans) shares nothing
 	// with the differencing kernel until the serialiser, so it runs on a
-	// forked side stream.  The differencing kernel is enqueued first so its
-	// (long, latency-bound) waves are resident before the CRC waves fill the
-	// issue slots they leave idle.
-	const bool serial = P->serial_crc || (P->crc_wide && !P->crc_wide_beside);   // the CRC pass on the run stream, first
+	// forked side stream.  (DG_SERIAL_CRC=1, an A/B bound: on the run stream,
+	// before the differencing.)
+	const bool serial = P->serial_crc;
 	hipStream_t cs = serial ? st : P->side;
 	const bool timed = P->timing && P->calls++ % P->every == 0;   // this run records its events
 	if (timed) P->cur = &P->ev[(size_t)kTimingEvents * (P->runs++ % P->slots)];
-	// event k on stream s: every stage event, or (DG_TIMING_DOMINANT) only
-	// the ones around the dominant kernel(s) (each extra timing event costs
-	// the run stream a few microseconds)
+	// event k: every stage event, or (DG_TIMING_DOMINANT) only the ones
+	// around the dominant kernel(s) (each extra timing event costs the run
+	// stream a few microseconds); nullptr = not recorded
+	auto ev = [&](int k) -> hipEvent_t { return timed && (timing_mask(P) & (1u << k)) ? P->cur[k] : nullptr; };
 	auto rec = [&](int k, hipStream_t s) -> hipError_t {
-		if (!timed || !(timing_mask(P) & (1u << k))) return hipSuccess;
-		return hipEventRecord(P->cur[k], s);
+		hipEvent_t e = ev(k);
+		return e ? hipEventRecord(e, s) : hipSuccess;
 	};
-	// member plans: the per-span combine (crc_finalize) waits on the run
-	// stream for the chains.  Enqueued right after the row pass, its waves
-	// queue behind the chains' full grid and slowed the routed chain of c3s
-	// by 13 % (40.9 vs 36.2 ms, profiles/r05_experiments.md).
+
+	// ── hints (the run's bytes do not depend on them) ──
 	// Automatic member mode: a batch whose every pair the last completed
 	// member-mode run of this plan routed to the plain chain (shift and
 	// transposition pairs, c3s / c4o) runs as a plain plan, the member kernel
 	// and its serialiser skipped, except every kProbeEvery-th run, which
-	// refreshes the count.  (A hint only: the output bytes do not depend on
-	// it.)
+	// refreshes the count.
 	bool mem = P->members;
 	if (mem && P->route_min && P->route_fb.read() >= P->n) {
 		if (++P->plain_streak < kProbeEvery) mem = false;
 		else P->plain_streak = 0;
 	}
 	++(mem ? P->member_runs : P->plain_runs);
-	const bool late_fin = mem && P->crc_late_fin && !serial && !P->crc_wide && !P->fused;
+	// member plans: the per-span combine (crc_finalize) waits on the run
+	// stream for the chains.  Enqueued right after the row pass, its waves
+	// queue behind the chains' full grid and slowed the routed chain of c3s
+	// by 13 % (40.9 vs 36.2 ms, profiles/r05_experiments.md).
+	const bool late_fin = mem && !serial;
 	// automatic member mode: when the last completed run of this plan routed
 	// more pairs to the plain chain than one round of chains fills (16 per
 	// CU), the routed chain's grid waits for the CRC pass to end.  Dispatched
 	// beside the pass's resident blocks, the chains land unevenly over the
 	// SIMDs and the second round's last pairs trail: c3s 39.1 -> 35.7 ms
 	// (profiles/r06_experiments.md).  Batches that route fewer pairs keep the
-	// pass beside the member chain, whose shadow it is at c6.  (A hint only:
-	// the run's bytes do not depend on it.)
-	const bool chain_join = mem && !serial && !P->skip_crc &&
-	                        (P->chain_join || (P->route_min && P->route_fb.read() > 16u * ctx->n_cu));
-	auto crc_args = [&]() {
-		CrcArgs a{};
-		a.arena[0] = d_ref;
-		a.arena[1] = d_ver;
-		a.spans = P->d_crc_spans_r.as<CrcSpanDev>();
-		a.segs = P->d_crc_segs.as<CrcSegDev>();
-		a.n_segs = P->n_crc_segs;
-		a.n_spans = P->n_crc_spans;
-		a.tables = ctx->d_crc_tables;
-		a.seg_crc = P->d_seg_crc.as<uint64_t>();
-		a.out = P->d_crc.as<uint64_t>();
-		a.xinv = ctx->d_xinv;
-		a.kseg = ctx->kseg;
-		a.prio_flag = kCrcPrioFlag && mem ? P->d_prio_flag.as<uint32_t>() : nullptr;
-		return a;
-	};
-#ifndef DG_CRC5_ALL   // A/B: the five-bit row pass beside the onepass kernel too
-#define DG_CRC5_ALL 0
-#endif
-	constexpr bool kCrc5All = DG_CRC5_ALL != 0;
+	// pass beside the member chain, whose shadow it is at c6.
+	const bool chain_join = mem && !serial && !P->skip_crc && P->route_min && P->route_fb.read() > 16u * ctx->n_cu;
+
+	CrcArgs c{};
+	c.arena[0] = d_ref;
+	c.arena[1] = d_ver;
+	c.spans = P->d_crc_spans_r.as<CrcSpanDev>();
+	c.segs = P->d_crc_segs.as<CrcSegDev>();
+	c.n_segs = P->n_crc_segs;
+	c.n_spans = P->n_crc_spans;
+	c.tables = ctx->d_crc_tables;
+	c.seg_crc = P->d_seg_crc.as<uint64_t>();
+	c.out = P->d_crc.as<uint64_t>();
+	c.xinv = ctx->d_xinv;
+	c.kseg = ctx->kseg;
+	c.prio_flag = kCrcPrioFlag && mem ? P->d_prio_flag.as<uint32_t>() : nullptr;
+	// the CRC pass on cs, then (side stream) the event the run stream joins on
 	auto run_crc = [&]() -> int {
 		HIPCHK(ctx, rec(0, cs));
-		const CrcArgs a = crc_args();
-		// beside the differencing: 2 blocks per CU per round of differencing
-		// waves (16 per CU), so the CRC neither crowds one round out nor
-		// trails a multi-round batch (C2: 4096 pairs -> 512 blocks)
-		const uint32_t rounds = (P->n + 16u * ctx->n_cu - 1) / (16u * ctx->n_cu);
-		if (!P->skip_crc) {
-			if (P->crc_wide) HIPCHK(ctx, launch_crc_wide(a, ctx->n_cu, cs));
+		if (!P->skip_crc) {   // (DG_SKIP_CRC=1, an A/B bound: no CRC kernels, wrong header CRCs)
+			// beside the differencing: 2 blocks per CU per round of differencing
+			// waves (16 per CU), so the CRC neither crowds one round out nor
+			// trails a multi-round batch (C2: 4096 pairs -> 512 blocks)
+			// (correcting plans: V's CRC runs beside the latency-bound V scan
+			// with its whole grid; capped at 2 blocks per CU it took 0.97 ms
+			// there instead of 0.71: C4 731 -> 813 GiB/s)
+			const uint32_t rounds = (P->n + 16u * ctx->n_cu - 1) / (16u * ctx->n_cu);
+			const uint32_t cap = serial || P->crc_fused ? 0u : 2u * ctx->n_cu * std::max(rounds, 1u);
 			// (member plans: the five-bit row pass, 3.25 KiB of LDS: the byte-table
 			// pass's 16 KiB blocks find no room beside the member kernel and trail
 			// it; the member waves run at a higher issue priority, so the pass
 			// takes the VALU slots they leave: C3 +3 %, c6 +10 % over round 4's
 			// lane-contiguous pass, profiles/r05_experiments.md)
-			// (correcting plans: V's CRC runs beside the latency-bound V scan
-			// with its whole grid; capped at 2 blocks per CU it took 0.97 ms
-			// there instead of 0.71: C4 731 -> 813 GiB/s)
-			else HIPCHK(ctx, launch_crc(a, cs, P->serial_crc || P->crc_fused ? 0u : 2u * ctx->n_cu * std::max(rounds, 1u),
-			                            mem || kCrc5All ? kCrcPassRows5 : kCrcPassRows, !late_fin));
+			HIPCHK(ctx, launch_crc(c, cs, cap, mem ? kCrcPassRows5 : kCrcPassRows, !late_fin));
 		}
 		HIPCHK(ctx, rec(1, cs));
+		if (!serial) HIPCHK(ctx, hipEventRecord(P->ev_join, cs));
 		return DG_OK;
 	};
 	// differencing -> COPY records + per-pair delta sizes
@@ -1286,161 +1320,95 @@ int dg_encode_plan_run(dg_encode_plan_t* P, const uint8_t* d_ref, const uint8_t*
 		a.n_tables = P->n_tables;
 		a.table_locks = P->d_locks.as<uint32_t>();
 		a.table_tags = P->d_tags.as<uint32_t>();
-		a.buf_cap = (uint32_t)P->opts.buf_cap;
-		a.dbg = P->dbg;
-		a.stats = P->algo == DG_ALGO_CORRECTING ? P->stats : nullptr;
-		if (P->algo == DG_ALGO_ONEPASS) {
-			if (P->fused) {
-				a.out = d_out;
-				a.out_cap = out_cap;
-				a.offsets = d_offsets;
-				a.lookback = P->d_lookback.as<unsigned long long>();
-				HIPCHK(ctx, hipMemsetAsync(P->d_lookback.p, 0, 8ull * P->n, st));
-			}
-			if (mem) {
-				SpecArgs m{};
-				m.ref = d_ref;
-				m.ver = d_ver;
-				m.pairs = a.pairs;
-				m.pplan = a.pplan;
-				m.chunks = P->d_chunks.as<uint2>();
-				m.mem_s = P->d_mem_s.as<uint32_t>();
-				m.n_mem = P->d_nmem.as<uint32_t>();
-				m.srec = P->d_srec.as<uint32_t>();
-				m.csum = P->d_csum.as<uint32_t>();
-				m.cmap = P->d_cmap.as<uint32_t>();
-				a.csum = m.csum;
-				a.cmap = m.cmap;
-				a.seg = P->d_seg.as<uint32_t>();
-				a.nseg = P->d_nseg.as<uint32_t>();
-				a.route_min = P->route_min;
-				a.mem_s = m.mem_s;
-				a.n_mem = m.n_mem;
-				a.srec = m.srec;
-				HIPCHK(ctx, launch_members(m, P->n_chunks, ctx->n_cu, st));
-				if (kCrcPrioFlag) HIPCHK(ctx, hipMemsetD32Async(P->d_prio_flag.p, 1, 1, st));   // the rows pass to priority 1
-				HIPCHK(ctx, rec(6, st));
-				if (P->route_min) a.route_cnt = P->d_route_cnt.as<uint32_t>();
-				HIPCHK(ctx, launch_onepass(a, a.p, P->aligned16, st, chain_join ? P->ev_join : nullptr));
-			} else {
-				if (P->op_crc) {
-					a.crc_out = P->d_crc.as<uint64_t>();
-					a.crc_tab = ctx->d_crc_tables;
-				}
-				HIPCHK(ctx, launch_onepass(a, a.p, P->aligned16, st));
-			}
-		} else if (P->algo == DG_ALGO_GREEDY) {
-			// zeroed bucket counts, the seed index of every R, then the V scan
-			GreedyArgs g{};
-			g.ref = d_ref;
-			g.ver = d_ver;
-			g.pairs = a.pairs;
-			g.pplan = a.pplan;
-			g.n_pairs = P->n;
-			g.p = a.p;
-			g.splay = (uint32_t)((P->opts.flags >> DG_OPT_SPLAY) & 1);
-			g.max_seeds = (uint32_t)P->max_seeds;
-			g.heads = P->d_ctab.as<uint32_t>();
-			g.ent = P->d_gent.as<uint2>();
-			g.rec = a.rec;
-			g.n_rec = a.n_rec;
-			g.dsize = a.dsize;
-			g.status = d_status;
-			HIPCHK(ctx, launch_greedy(g, P->greedy_heads, st,
-			                          timed && (timing_mask(P) & (1u << 7)) ? P->cur[7] : nullptr));
-		} else {
-			// fresh R indexes (~0 = empty slot), then build + scan
-			a.ctab = P->d_ctab.as<uint32_t>();
-			a.kcls = P->d_kcls.as<uint64_t>();
-			a.max_seeds = (uint32_t)P->max_seeds;
-			// the LDS build writes every slot of every index; the global
-			// build only fills, so its tables start empty (~0)
-			a.gpairs = P->d_gpairs.as<uint32_t>();
-			a.n_gpairs = P->n_gpairs;
-			HIPCHK(ctx, launch_correcting_clear(a, st));
-			if (P->crc_fused) {
-				a.crc_out = P->d_crc.as<uint64_t>();
-				a.crc_tab = ctx->d_crc_tables;
-				a.crc_k32 = ctx->d_k32;
-			}
-			HIPCHK(ctx, launch_correcting(a, a.p, st, P->corr_lds_cap, P->qmin,
-			                              timed && (timing_mask(P) & (1u << 7)) ? P->cur[7] : nullptr,
-			                              (P->crc_fused || P->crc_wide_beside) && !serial ? P->ev_fork : nullptr));
+		if (P->fused) {   // (DG_FUSED=1, A/B: the onepass waves place and serialise their deltas)
+			a.out = d_out;
+			a.out_cap = out_cap;
+			a.offsets = d_offsets;
+			a.lookback = P->d_lookback.as<unsigned long long>();
+			HIPCHK(ctx, hipMemsetAsync(P->d_lookback.p, 0, 8ull * P->n, st));
 		}
+		int rc;
+		if (P->algo == DG_ALGO_ONEPASS)
+			rc = enqueue_onepass(P, a, mem, ev(6), chain_join ? P->ev_join : nullptr, st);
+		else if (P->algo == DG_ALGO_GREEDY)
+			rc = enqueue_greedy(P, a, ev(7), st);
+		else
+			rc = enqueue_correcting(P, a, ev(7), P->crc_fused && !serial ? P->ev_fork : nullptr, st);
+		if (rc != DG_OK) return rc;
 		if (P->algo == DG_ALGO_ONEPASS) HIPCHK(ctx, rec(7, st));
 		HIPCHK(ctx, rec(3, st));
 		return DG_OK;
 	};
+
+	// ── {differencing, CRC} ──
 	int rc;
 	if (serial) {
 		if ((rc = run_crc()) != DG_OK) return rc;
 		if ((rc = run_diff()) != DG_OK) return rc;
-	} else if (P->crc_fused || P->crc_wide_beside) {
+	} else if (P->crc_fused) {
 		// the build writes R's CRC; V's CRC forks after the build (ev_fork,
 		// recorded by launch_correcting) and runs beside the V scan
 		if ((rc = run_diff()) != DG_OK) return rc;
 		HIPCHK(ctx, hipStreamWaitEvent(cs, P->ev_fork, 0));
 		if ((rc = run_crc()) != DG_OK) return rc;
-		HIPCHK(ctx, hipEventRecord(P->ev_join, cs));
 	} else {
 		if (kCrcPrioFlag && mem) HIPCHK(ctx, hipMemsetD32Async(P->d_prio_flag.p, 0, 1, st));
 		HIPCHK(ctx, hipEventRecord(P->ev_fork, st));
 		HIPCHK(ctx, hipStreamWaitEvent(cs, P->ev_fork, 0));
-		if (P->crc_first || chain_join) {   // CRC waves dispatched first (A/B), or the routed chain after them
+		if (chain_join) {   // the routed chain waits for the CRC pass (ev_join)
 			if ((rc = run_crc()) != DG_OK) return rc;
-			if (chain_join) HIPCHK(ctx, hipEventRecord(P->ev_join, cs));
 			if ((rc = run_diff()) != DG_OK) return rc;
 		} else {
+			// the differencing kernel first, so its (long, latency-bound) waves
+			// are resident before the CRC waves fill the issue slots they leave
 			if ((rc = run_diff()) != DG_OK) return rc;
 			if ((rc = run_crc()) != DG_OK) return rc;
 		}
-		HIPCHK(ctx, hipEventRecord(P->ev_join, cs));
 	}
+
 	if (P->fused) {
-		// the differencing kernel placed and serialised every delta; only the
-		// header CRCs remain, once the CRC stream has joined
+		// (DG_FUSED=1, A/B) the differencing kernel placed and serialised every
+		// delta; only the header CRCs remain, once the CRC stream has joined
 		if (!serial) HIPCHK(ctx, hipStreamWaitEvent(st, P->ev_join, 0));
 		HIPCHK(ctx, rec(4, st));
 		HIPCHK(ctx, launch_crc_patch(d_out, d_offsets, P->d_crc.as<uint64_t>(), d_status, P->n, st));
 		HIPCHK(ctx, rec(5, st));
 		return DG_OK;
 	}
-	// 3. exclusive scan of sizes -> packed offsets
+
+	// ── exclusive scan of the delta sizes -> packed offsets ──
 	HIPCHK(ctx, launch_scan(P->d_dsize.as<uint64_t>(), d_offsets, P->n, st,
 	                        mem && P->route_min ? P->d_route_cnt.as<uint32_t>() : nullptr, P->route_fb.d));
-	SerArgs s{};
-	s.ver = d_ver;
-	s.pairs = P->d_pairs.as<PairDev>();
-	s.pplan = P->d_pplan.as<PairPlanDev>();
-	s.rec = P->d_rec.as<uint32_t>();
-	s.rec_words = P->algo != DG_ALGO_CORRECTING ? kRecWordsOnepass : kRecWordsCorrecting;
-	s.n_rec = P->d_nrec.as<uint32_t>();
-	s.crc = P->d_crc.as<uint64_t>();
-	s.offsets = d_offsets;
-	s.out = d_out;
-	s.out_cap = out_cap;
-	s.status = d_status;
-	s.n_pairs = P->n;
-	// 4. serialise.  Member plans serialise everything but the header CRCs
-	//    (the CRC stream may still be running beside the chains), then join
-	//    and patch them in; the others join first (below)
 	HIPCHK(ctx, rec(4, st));
-	if (mem) {   // the chains' segment lists, one wave per chunk
+
+	// ── serialise + join ──
+	if (mem) {
+		// the chains' segment lists, one wave per chunk: everything but the
+		// header CRCs (the CRC stream may still be running beside the chains),
+		// then the join, the CRC's combine and the header patch
 		const MemSerArgs m = mem_ser_args(P, d_ver, d_out, out_cap, d_offsets, d_status);
 		HIPCHK(ctx, launch_member_serialize(m, P->n_chunks, ctx->n_cu, st));
-		if (!serial) HIPCHK(ctx, hipStreamWaitEvent(st, P->ev_join, 0));   // join the CRCs
-		if (late_fin && !P->skip_crc) HIPCHK(ctx, launch_crc_finalize(crc_args(), st));
-		HIPCHK(ctx, launch_crc_patch(d_out, d_offsets, P->d_crc.as<uint64_t>(), d_status, P->n, st));
-	} else if (P->crc_patch) {
-		HIPCHK(ctx, launch_serialize_wave(s, st));
 		if (!serial) HIPCHK(ctx, hipStreamWaitEvent(st, P->ev_join, 0));
+		if (late_fin && !P->skip_crc) HIPCHK(ctx, launch_crc_finalize(c, st));
 		HIPCHK(ctx, launch_crc_patch(d_out, d_offsets, P->d_crc.as<uint64_t>(), d_status, P->n, st));
 	} else {
 		// the CRC pass (beside the differencing) has normally finished by
-		// now: join it first and let the serialiser write the header CRCs,
-		// one dependent launch (crc_patch_kernel, ~12 us at C2) fewer
+		// now: join it first and let the serialiser write the header CRCs
+		// (a crc_patch_kernel after it is one dependent launch, ~12 us at C2, more)
 		if (!serial) HIPCHK(ctx, hipStreamWaitEvent(st, P->ev_join, 0));
-		s.crc_in = 1;
+		SerArgs s{};
+		s.ver = d_ver;
+		s.pairs = P->d_pairs.as<PairDev>();
+		s.pplan = P->d_pplan.as<PairPlanDev>();
+		s.rec = P->d_rec.as<uint32_t>();
+		s.rec_words = P->algo != DG_ALGO_CORRECTING ? kRecWordsOnepass : kRecWordsCorrecting;
+		s.n_rec = P->d_nrec.as<uint32_t>();
+		s.crc = P->d_crc.as<uint64_t>();
+		s.offsets = d_offsets;
+		s.out = d_out;
+		s.out_cap = out_cap;
+		s.status = d_status;
+		s.n_pairs = P->n;
 		HIPCHK(ctx, launch_serialize_wave(s, st));
 	}
 	HIPCHK(ctx, rec(5, st));
@@ -1668,13 +1636,6 @@ int dg_decode_plan_run(dg_decode_plan_t* P, const uint8_t* d_ref, const uint8_t*
 	// empty stages the round-4 layout also recorded cost C5 ~8 %)
 	if (ev) HIPCHK(ctx, hipEventRecord(ev[0], st));
 	DecodeArgs a{};
-	{
-		static const uint32_t dbg = [] {
-			const char* e = ab_env("DG_DEBUG_BITS");
-			return e ? (uint32_t)strtoul(e, nullptr, 0) : 0u;
-		}();
-		a.dbg = dbg;
-	}
 	a.ref = d_ref;
 	a.delta = d_delta;
 	a.descs = P->d_desc.as<dg_decode_desc_dev>();

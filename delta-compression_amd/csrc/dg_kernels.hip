@@ -120,9 +120,6 @@ __global__ __launch_bounds__(kBlock) void crc_rows_wide_kernel(CrcArgs a) {
 #ifndef DG_CRC_PF5
 #define DG_CRC_PF5 4
 #endif
-#ifndef DG_CRC_BESIDE_WIDE
-#define DG_CRC_BESIDE_WIDE 0
-#endif
 #ifndef DG_CRC_PRIO   // A/B: issue priority of the rows pass beside another kernel (0..3)
 #define DG_CRC_PRIO 0
 #endif
@@ -342,16 +339,11 @@ hipError_t launch_synth_transpose(uint8_t* ref, uint8_t* ver, const SynthSpan* s
 
 // One wave per pair (dg_serialize_wave.h): DPP scans instead of block
 // barriers, 64 commands per tile staged in a 4 KiB LDS slice, so 32 pairs
-// per CU are in flight and their record / payload loads overlap.  The header
-// CRC bytes are left to crc_patch_kernel, so this kernel does not wait for
-// the CRC stream.
+// per CU are in flight and their record / payload loads overlap.  The CRC
+// stream has joined before it, so it writes the header CRC bytes itself.
 // (one record per lane per tile: 4 measured slower, C2 +18 %, C3 3.6x)
-#ifndef DG_SER_PIPE   // A/B: 1 = the LDS-DMA pipeline (serialize_pipe, 2 KiB stage), C2 37.7 -> 74.9 us
-#define DG_SER_PIPE 0
-#endif
-constexpr bool kSerPipe = DG_SER_PIPE != 0;
-constexpr uint32_t kSerWaveStage = kSerPipe ? 2048 : 4096;   // (pipeline rings beside a 2 KiB stage: 16 waves per CU)
-constexpr uint32_t kSerWaveLds = kSerPipe ? pipe_lds_bytes<kSerWaveStage>() : kSerWaveStage + 32;
+constexpr uint32_t kSerWaveStage = 4096;
+constexpr uint32_t kSerWaveLds = kSerWaveStage + 32;
 
 __global__ __launch_bounds__(64) void serialize_wave_kernel(SerArgs s) {
 	__shared__ __attribute__((aligned(16))) uint8_t stage[kSerWaveLds];
@@ -365,11 +357,11 @@ __global__ __launch_bounds__(64) void serialize_wave_kernel(SerArgs s) {
 	if (s.status[pair] != 0) return;
 	const PairDev pd = s.pairs[pair];
 	const PairPlanDev pp = s.pplan[pair];
-	const int32_t st = serialize_wave<kSerWaveStage, kSerPipe>(s.out + base, end - base, s.ver + pd.v_off,
-	                                                 (uint32_t)pd.v_len, s.rec + (uint64_t)s.rec_words * pp.rec_base,
-	                                                 s.rec_words, s.n_rec[pair], (sw_lds8*)stage);
+	const int32_t st = serialize_wave<kSerWaveStage>(s.out + base, end - base, s.ver + pd.v_off, (uint32_t)pd.v_len,
+	                                                 s.rec + (uint64_t)s.rec_words * pp.rec_base, s.rec_words,
+	                                                 s.n_rec[pair], (sw_lds8*)stage);
 	if (st != 0 && lane_id() == 0) s.status[pair] = st;
-	if (st == 0 && s.crc_in) {   // header bytes 9..24: CRC of R, CRC of V, big-endian (encoding.c:52-54)
+	if (st == 0) {   // header bytes 9..24: CRC of R, CRC of V, big-endian (encoding.c:52-54)
 		const uint32_t lane = lane_id();
 		if (lane < 16) {
 			const uint64_t c = s.crc[2ull * pair + (lane >> 3)];
@@ -379,7 +371,7 @@ __global__ __launch_bounds__(64) void serialize_wave_kernel(SerArgs s) {
 }
 
 // header bytes 9..24 (src/dst CRC, big-endian, encoding.c:52-54) of deltas
-// serialised before their CRCs were known
+// serialised before their CRCs were known (member plans)
 __global__ __launch_bounds__(256) void crc_patch_kernel(uint8_t* out, const uint64_t* offsets,
                                                         const uint64_t* crc, const int32_t* status,
                                                         uint32_t n) {
@@ -441,10 +433,6 @@ hipError_t launch_crc(const CrcArgs& a, hipStream_t st, uint32_t overlap_cap, in
 		if (cap && blocks > cap) blocks = cap;
 		if (pass == kCrcPassRows5)
 			hipLaunchKernelGGL(crc_rows_kernel<kCrcFive>, dim3(blocks), dim3(64 * kCrcWavesPerBlock), 0, st, a);
-#if DG_CRC_BESIDE_WIDE   // A/B: 16-byte pieces (32 KiB of tables) in one 4-wave block per CU beside the differencing
-		else if (cap)
-			hipLaunchKernelGGL(crc_rows_wide_kernel<256>, dim3(std::min<uint32_t>(blocks, cap / 2)), dim3(256), 0, st, a);
-#endif
 		else
 			hipLaunchKernelGGL(crc_rows_kernel<kCrcByte>, dim3(blocks), dim3(64 * kCrcWavesPerBlock), 0, st, a);
 	}
@@ -662,11 +650,7 @@ typedef uint32_t u32_u __attribute__((aligned(1)));
 // bytes at offsets clamped to rem - 1; never a byte outside [0, rem).
 // (Round 5 copied dword by dword and byte by byte, each store before the next
 // load: up to 6 dependent round trips per partial chunk.)
-#ifndef DG_DEC_TAIL1   // A/B: 0 = round 5's dword-then-byte loop
-#define DG_DEC_TAIL1 1
-#endif
 __device__ __forceinline__ void copy_tail(uint8_t* d, const uint8_t* s, uint32_t rem) {
-#if DG_DEC_TAIL1
 	if (rem >= 4) {
 		uint32_t w[4], o[4];
 #pragma unroll
@@ -685,11 +669,6 @@ __device__ __forceinline__ void copy_tail(uint8_t* d, const uint8_t* s, uint32_t
 		for (uint32_t k = 0; k < 3; ++k)
 			if (k < rem) d[k] = b[k];
 	}
-#else
-	const uint32_t nd = rem >> 2;
-	for (uint32_t k = 0; k < nd; ++k) *reinterpret_cast<u32_u*>(d + 4 * k) = *reinterpret_cast<const u32_u*>(s + 4 * k);
-	for (uint32_t k = 4 * nd; k < rem; ++k) d[k] = s[k];
-#endif
 }
 
 // Per-wave LDS scratch of the flat copy.
@@ -782,40 +761,6 @@ __device__ void dec_flat_batch(const DecCmd& c, bool inplace, uint8_t* O, const 
 		const uint64_t kl = ((uint64_t)rdlane((uint32_t)(c.len >> 32), kk) << 32) | rdlane((uint32_t)c.len, kk);
 		wave_memmove(O + kd, O + ks, kl);
 	}
-}
-
-// One batch in stream order (wave 0 of a window that is not order-free):
-// conflict check among the batch's commands, then the flat copy or the
-// strict memmove replay (apply.c:257-266), then a full wait.
-__device__ void dec_ordered_batch(const DecCmd& c, uint32_t n, bool inplace, uint8_t* O, const uint8_t* R,
-                                  const uint8_t* D, const DecScratch& x) {
-	const uint32_t lane = lane_id();
-	bool conflict = false;
-	const bool reads_buf = inplace && c.kind == 1;
-	for (uint32_t k = 0; k + 1 < n; ++k) {
-		const uint64_t ks = ((uint64_t)rdlane((uint32_t)(c.src >> 32), k) << 32) | rdlane((uint32_t)c.src, k);
-		const uint64_t kd = ((uint64_t)rdlane((uint32_t)(c.dst >> 32), k) << 32) | rdlane((uint32_t)c.dst, k);
-		const uint64_t kl = ((uint64_t)rdlane((uint32_t)(c.len >> 32), k) << 32) | rdlane((uint32_t)c.len, k);
-		const bool kreads = inplace && rdlane(c.kind, k) == 1;
-		if (c.mine && lane > k) {
-			if (overlap(kd, kl, c.dst, c.len)) conflict = true;
-			if (reads_buf && overlap(kd, kl, c.src, c.len)) conflict = true;
-			if (kreads && overlap(ks, kl, c.dst, c.len)) conflict = true;
-		}
-	}
-	if (__ballot(conflict) == 0) {
-		dec_flat_batch(c, inplace, O, R, D, x);
-	} else {
-		for (uint32_t k = 0; k < n; ++k) {
-			const uint32_t kk = rdlane(c.kind, k);
-			const uint64_t ks = ((uint64_t)rdlane((uint32_t)(c.src >> 32), k) << 32) | rdlane((uint32_t)c.src, k);
-			const uint64_t kd = ((uint64_t)rdlane((uint32_t)(c.dst >> 32), k) << 32) | rdlane((uint32_t)c.dst, k);
-			const uint64_t kl = ((uint64_t)rdlane((uint32_t)(c.len >> 32), k) << 32) | rdlane((uint32_t)c.len, k);
-			wave_memmove(O + kd, kk == 1 ? (inplace ? O + ks : R + ks) : D + ks, kl);
-		}
-	}
-	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-	__builtin_amdgcn_wave_barrier();
 }
 
 // ── windows that are not order-free (in-place deltas whose COPYs move):
@@ -1015,11 +960,8 @@ __device__ void dec_grouped_window(WP w, const uint16_t* cmds, uint32_t cnt, uin
 // (dg_crc.h).  The byte tables go to LDS at tb (256-byte aligned, inside the
 // dead doubling arrays), then the nibble table of x^(8 * 64 KiB) (the Horner
 // step of a wave's segments) at TK.
-#ifndef DG_DEC_CRC5   // A/B: the decode's CRC folds by five-bit tables (13 conflict-free lookups per piece)
-#define DG_DEC_CRC5 0
-#endif
-constexpr int kDecTab = DG_DEC_CRC5 ? kCrcFive : kCrcByte;
-constexpr uint32_t kDecTabWords = kDecTab == kCrcFive ? 32 * kCrc5Tabs8 : 8 * 256;
+constexpr int kDecTab = kCrcByte;
+constexpr uint32_t kDecTabWords = 8 * 256;
 struct DecCrc {
 	uint32_t tb;
 	const uint64_t* TK;
@@ -1029,7 +971,7 @@ __device__ __forceinline__ DecCrc dec_crc_tables(uint16_t* NX, const DecodeArgs&
 	const uint32_t tid = threadIdx.x;
 	const uint32_t base = lds_addr(NX), tb = (base + 255u) & ~255u;
 	uint64_t* T = reinterpret_cast<uint64_t*>(NX) + (tb - base) / 8;
-	const uint64_t* src = a.tables + (kDecTab == kCrcFive ? kCrc5R8 : kCrcRows8);
+	const uint64_t* src = a.tables + kCrcRows8;
 	for (uint32_t k = tid; k < kDecTabWords; k += kDecBlock) T[k] = src[k];
 	uint64_t* TK = T + kDecTabWords;
 	const uint64_t* KF = a.tables + 8 * 256 + kCrcLevels * kCrcNibTabWords;
@@ -1380,11 +1322,7 @@ __global__ __launch_bounds__(kDecBlock) __attribute__((amdgpu_waves_per_eu(4, 8)
 		DPROF_ADD(DP_HDR, th0);
 		DPROF_T(tc0);
 		// ── 6. apply ──
-#ifdef DG_AB_SWITCHES
-		if (!st && !(a.dbg & 0x100)) {   // 0x100: skip the apply (A/B builds only, never the product)
-#else
 		if (!st) {
-#endif
 			if (free_win) {
 				for (uint32_t b = wave; b < nb; b += kDecWaves) {
 					DPROF_INC(DP_BATCHES);
@@ -1399,15 +1337,6 @@ __global__ __launch_bounds__(kDecBlock) __attribute__((amdgpu_waves_per_eu(4, 8)
 					DPROF_ADD(DP_C_FLAT, tq1);
 				}
 			} else {
-#ifdef DG_AB_SWITCHES
-				if (a.dbg & 0x200) {   // A/B (DG_DEBUG_BITS=0x200): the round-2 one-wave replay
-					if (wave == 0)
-						for (uint32_t b = 0; b < nb; ++b) {
-							const DecCmd c = dec_cmd(w, cmds, 64 * b, cnt, pos);
-							dec_ordered_batch(c, cnt - 64 * b < 64 ? cnt - 64 * b : 64, inplace, O, R, D, xs);
-						}
-				} else
-#endif
 				dec_grouped_window(w, cmds, cnt, pos, inplace, O, R, D, grp);
 			}
 		}

@@ -155,11 +155,6 @@ struct ChunkLds {
 // ds_read_b128, but it stalls the LDS pipe: on C3 SQ_LDS_UNALIGNED_STALL was
 // 61 % of the member kernel's LDS-active cycles (profiles/r05_member_census.md).
 __device__ __forceinline__ uint4 lds16(const uint8_t* s, uint32_t o) {
-#ifdef DG_LDS16_UNALIGNED   // A/B variant: the unaligned ds_read_b128
-	uint4 w;
-	__builtin_memcpy(&w, s + o, 16);
-	return w;
-#endif
 	const uint32_t* d = reinterpret_cast<const uint32_t*>(s + (o & ~3u));
 	const uint32_t sh = (o & 3u) * 8u;
 	const uint32_t d0 = d[0], d1 = d[1], d2 = d[2], d3 = d[3], d4 = d[4];
@@ -344,15 +339,12 @@ struct StageRegs {
 	uint4 v[kStageRows], r[kStageRows];
 };
 
-// A wave's walk over its contiguous run of (pair, chunk) jobs: the jobs are
-// laid out pair after pair, chunk after chunk, so the next job follows from
-// this one and only a new pair's descriptors are loaded (wave-uniform).
+// A wave's (pair, chunk) job and its pair's descriptors (wave-uniform).
 struct JobCursor {
 	uint32_t pair, c, n_chunks, chunk_base;
 	uint32_t vl, rl;
-	uint64_t v_off, r_off, mem_base, q, q_magic, rec_base;
-	template <class Args>
-	__device__ void load_pair(const Args& a) {
+	uint64_t v_off, r_off, mem_base, q, q_magic;
+	__device__ void load_pair(const SpecArgs& a) {
 		// (wave-uniform: into SGPRs, so the member kernel's 72-VGPR budget
 		// holds no 64-bit descriptor copies)
 		const PairDev& pd = a.pairs[pair];
@@ -366,24 +358,12 @@ struct JobCursor {
 		q_magic = uni64(pp.q_magic);
 		chunk_base = uni(pp.chunk_base);
 		n_chunks = uni(pp.n_chunks);
-		rec_base = uni64(pp.rec_base);
 	}
-	template <class Args>
-	__device__ void start(const Args& a, uint32_t job) {
+	__device__ void start(const SpecArgs& a, uint32_t job) {
 		const uint2 jb = a.chunks[job];
 		pair = uni(jb.x);
 		c = uni(jb.y);
 		load_pair(a);
-	}
-	template <class Args>
-	__device__ void next(const Args& a) {
-		if (c + 1 < n_chunks) {
-			++c;
-		} else {
-			++pair;
-			c = 0;
-			load_pair(a);
-		}
 	}
 };
 
@@ -610,9 +590,6 @@ __device__ __forceinline__ void member_chunk(const SpecArgs& a, ChunkLds& L, con
 			const bool in = shrt && P > done && P <= done + 64;
 			const uint64_t RM = __ballot(in);
 			if (!RM) break;
-#ifdef DG_MEM_SKIP_SHORT   // timing variants only
-			break;
-#endif
 			MPROF_INC(MP_ROUNDS, 1);
 			const uint32_t hi = 63u - (uint32_t)__builtin_clzll(RM);
 			const uint32_t B = rdlane(P, hi) - done;   // live steps of the round
@@ -635,26 +612,16 @@ __device__ __forceinline__ void member_chunk(const SpecArgs& a, ChunkLds& L, con
 			uint32_t sV = kSentinel, fVl = 0, fRl = 1;   // (fVl, fRl: window hashes)
 			if (live) {
 				const uint4 wv = lds16(SV, ms_j + t), wr = lds16(SR, ms_j + t);
-#ifdef DG_MEM_SKIP_FP   // timing variants only: no fingerprints
-				sV = wv.x % 16411u;
-#else
 				sV = slot_of(fp16_dot(wv.x, wv.y, wv.z, wv.w), mq, q, qmag);
-#endif
 				fVl = win_hash(wv);
 				fRl = win_hash(wr);
 			}
-#ifndef DG_MEM_SKIP_A
 			if (live && !isT) fs.add(fVl);
-#endif
 			lds_order();
 			const uint64_t mem = live ? lanes_mask(fb, mt_j + 1) : 0ull;   // this lane's member
 			bool bad = false;
 			// (A) off T: steps whose R hash may equal another step's V hash
-#ifdef DG_MEM_SKIP_A
-			for (uint64_t w = 0; w; w &= w - 1) {
-#else
 			for (uint64_t w = __ballot(live && !isT && fs.has(fRl)); w; w &= w - 1) {
-#endif
 				MPROF_INC(MP_FLAGGED, 1);
 				const uint32_t Lx = ffs64(w);
 				const uint64_t others = ((uint64_t)rdlane((uint32_t)(mem >> 32), Lx) << 32 | rdlane((uint32_t)mem, Lx)) &
@@ -704,11 +671,7 @@ __device__ __forceinline__ void member_chunk(const SpecArgs& a, ChunkLds& L, con
 		MPROF_ADD(MP_SHORT, tq0);
 		MPROF_T(tl0);
 		// ── long members (64 <= T < 512): 64-step rows, history in VGPRs ──
-#ifdef DG_MEM_SKIP_LONG   // timing variants only
-		for (uint64_t LM = 0; LM; LM &= LM - 1) {
-#else
 		for (uint64_t LM = __ballot(known && !shrt && T < 64u * kLongChunks); LM; LM &= LM - 1) {
-#endif
 			MPROF_INC(MP_LONG_N, 1);
 			const uint32_t M = ffs64(LM);
 			const uint32_t s0 = rdlane(s, M), tl = rdlane(T, M), sn0 = rdlane(sn, M);
@@ -876,7 +839,6 @@ __device__ __forceinline__ void put_bulk(P dst, bool valid, uint32_t my, uint32_
 	}
 }
 
-constexpr uint32_t kMemSerStage = 4096;
 #ifndef DG_MSER_WAVES
 #define DG_MSER_WAVES 16
 #endif
@@ -886,143 +848,21 @@ constexpr uint32_t kSerWavesPerCu = DG_MSER_WAVES;   // persistent serialiser wa
 #endif
 constexpr uint32_t kSerWavesSparse = DG_MSER_WAVES_SPARSE;   // ... for a sparse batch (delta < |V| / 2)
 
-// one job's inputs, loaded a job ahead (descriptors wave-uniform)
-struct SerFetch {
-	JobCursor J;
-	uint32_t cnt, boff, first;
-	int32_t st;
-	uint64_t base, end, slot0;
-	uint4 v[kStageRows];   // the chunk's staged V bytes (as the member kernel's)
-	uint4 r;               // member record of this lane (first 64)
-};
-
-// every load unconditional (no branch for the compiler to drain before the
-// loads of the job after it are issued)
-__device__ __forceinline__ void ser_fetch(const MemSerArgs& a, SerFetch& F) {
-	const uint32_t lane = lane_id();
-	const JobCursor& J = F.J;
-	F.st = a.status[J.pair];
-	F.base = a.offsets[J.pair];
-	F.end = a.offsets[J.pair + 1];
-	const uint2 cm = *(const uint2*)(a.cmap + 2ull * (J.chunk_base + J.c));
-	F.cnt = cm.x;
-	F.boff = cm.y;
-	F.slot0 = J.mem_base + (uint64_t)J.c * kMemChunkSlots;
-	const int64_t g0 = (int64_t)J.c * kMemChunk - 16;
-	const uint8_t* V = a.ver + J.v_off;
-#pragma unroll
-	for (uint32_t k = 0; k < kStageRows; ++k) F.v[k] = load16_async(V, g0 + 1024 * k + 16 * lane, J.vl);
-	F.r = make_uint4(0u, 0u, 0u, 0u);   // (slots 0..63 of the chunk's 129, only the bulk members')
-	if (lane < F.cnt) F.r = *(const uint4*)(a.srec + 4ull * (F.slot0 + lane));
-	F.first = a.mem_s[F.slot0];
-}
-
-// Member-mode serialisation: each chunk's job writes its bulk piece (the
-// members the chain took as they are, from the member records, payloads from
-// the chunk's V bytes in LDS) at the piece's byte offset, plus the pair's
-// segments 2c, 2c + 1 (record runs of the chain's own epochs, the tail), so
-// all the chunks of a pair serialise at once.  Persistent waves over
-// contiguous jobs, each job's inputs loaded while the previous one is written.
-// (ADD payloads read straight from V instead of the staged chunk measured
-// slower even on the sparsest bench batch, c6: profiles/r04_experiments.md.)
-__device__ __forceinline__ void member_serialize(const MemSerArgs& a, uint32_t j0, uint32_t j1, uint8_t* vbuf,
-                                                 uint8_t* stage) {
-	const uint32_t lane = lane_id();
-	SerFetch F, N;
-	F.J.start(a, j0);
-	ser_fetch(a, F);
-	for (uint32_t j = j0; j < j1; ++j) {
-		if (j + 1 < j1) {
-			N.J = F.J;
-			N.J.next(a);
-			ser_fetch(a, N);
-		}
-		const uint32_t vl = F.J.vl;
-		const uint8_t* V = a.ver + F.J.v_off;
-		if (F.st == 0) {
-			if (F.end > a.out_cap) {
-				if (F.J.c == 0 && lane == 0) a.status[F.J.pair] = 7;
-			} else {
-				uint8_t* out = a.out + F.base;
-				if (F.J.c == 0) put_header(out, vl);
-				if (F.cnt) {
-					// ADD payloads from the chunk's V bytes staged in LDS
-					const int64_t g0 = (int64_t)F.J.c * kMemChunk - 16;
-					const uint8_t* vb = vbuf;
-					lds_order();
-#pragma unroll
-					for (uint32_t k = 0; k < kStageRows; ++k)
-						if (1024 * k + 16 * lane < kStage)
-							*(uint4*)(vbuf + 1024 * k + 16 * lane) = stage_piece(F.v[k], V, g0 + 1024 * k + 16 * lane, vl);
-					lds_order();
-					uint64_t pos = F.boff;
-					uint32_t prev_end = F.first;
-					for (uint32_t t0 = 0; t0 < F.cnt; t0 += 64) {
-						uint4 r = F.r;
-						if (t0 && t0 + lane < F.cnt) r = *(const uint4*)(a.srec + 4ull * (F.slot0 + t0 + lane));
-						const bool valid = t0 + lane < F.cnt;
-						const uint32_t x = r.x, len = r.y;
-						const uint32_t last = valid ? x + len : 0u;
-						uint32_t prev = wave_shr1(last);
-						if (lane == 0) prev = prev_end;
-						const uint32_t gap = x - prev;
-						const uint32_t sz = valid ? 13u + (gap ? 9u + gap : 0u) : 0u;
-						const uint32_t incl = wave_incl_scan(sz);
-						const uint32_t my = incl - sz;
-						const uint32_t S = rdlane(incl, 63);
-						if (S <= kMemSerStage) {
-							lds_order();
-							put_bulk(stage, valid, my, prev, x, len, r.z, vb, g0);
-							lds_order();
-							// flush: head bytes to a 16-byte boundary, 16-byte stores, tail bytes
-							uint8_t* dst = out + pos;
-							const uint32_t head = umin32((uint32_t)((16u - ((uintptr_t)dst & 15u)) & 15u), S);
-							if (lane < head) dst[lane] = stage[lane];
-							const uint32_t nq = (S - head) / 16;
-							uint4* dq = reinterpret_cast<uint4*>(dst + head);
-							for (uint32_t k = lane; k < nq; k += 64) {
-								uint4 w;
-								__builtin_memcpy(&w, stage + head + 16 * k, 16);
-								dq[k] = w;
-							}
-							const uint32_t tail0 = head + 16 * nq;
-							if (lane < S - tail0) dst[tail0 + lane] = stage[tail0 + lane];
-						} else {
-							put_bulk(out + pos, valid, my, prev, x, len, r.z, vb, g0);
-						}
-						pos += S;
-						const uint64_t has = __ballot(valid);
-						prev_end = rdlane(last, 63u - (uint32_t)__builtin_clzll(has));
-					}
-				}
-				// the chain's own record runs and the tail (segments 2c, 2c + 1;
-				// the pair's last chunk takes the rest)
-				const uint32_t ns = a.nseg[F.J.pair];
-				const uint32_t* seg = a.seg + 4ull * ((uint64_t)F.J.chunk_base + 2ull * F.J.pair);
-				const uint32_t k1 = F.J.c + 1 == F.J.n_chunks ? ns : umin32(2 * F.J.c + 2, ns);
-				for (uint32_t k = 2 * F.J.c; k < k1; ++k) {
-					const uint4 e = *(const uint4*)(seg + 4ull * k);
-					uint8_t* o = out + e.z;
-					if (e.x == kSegTail) {
-						const uint64_t n = put_tail(o, V, vl, e.w);
-						if (e.z + n != F.end - F.base && lane == 0) a.status[F.J.pair] = 12;   // DG_ERR_INTERNAL: sizes disagree
-					} else {
-						const RecWords src{a.rec + (uint64_t)kRecWordsOnepass * (F.J.rec_base + e.x), kRecWordsOnepass};
-						serialize_run<kMemSerStage>(o, V, vl, src, e.y, e.w, (sw_lds8*)stage);
-					}
-				}
-			}
-		}
-		F = N;
-	}
-}
-
-// ── member-mode serialisation, software-pipelined (DG_MSER_PIPE, default) ──
+// ── member-mode serialisation, software-pipelined ──
 //
-// member_serialize waits, for every job, for the next job's loads issued
-// after this job's stores (loads and stores share the vmcnt counter, which
-// drains in issue order: the copy of the prefetched registers waits for the
-// stores too).  Here the next job's V bytes and member records go by LDS-DMA
+// Each chunk's job writes its bulk piece (the members the chain took as they
+// are, from the member records, payloads from the chunk's V bytes in LDS) at
+// the piece's byte offset, plus the pair's segments 2c, 2c + 1 (record runs of
+// the chain's own epochs, the tail), so all the chunks of a pair serialise at
+// once.  Persistent waves over contiguous jobs.  (ADD payloads read straight
+// from V instead of the staged chunk measured slower even on the sparsest
+// bench batch, c6: profiles/r04_experiments.md.)
+//
+// A serialiser that prefetches the next job into registers waits, for every
+// job, for those loads issued after this job's stores (loads and stores share
+// the vmcnt counter, which drains in issue order: the copy of the prefetched
+// registers waits for the stores too; round 5's member_serialize, DESIGN.md,
+// rejected experiments).  Here the next job's V bytes and member records go by LDS-DMA
 // into rings of two slots, its descriptors by scalar loads (lgkmcnt, not
 // vmcnt), and a job's flush is a fixed count of buffer stores, so one
 // hand-counted s_waitcnt vmcnt(kMserTileStores) at the top of the next job
@@ -1248,18 +1088,10 @@ __device__ __forceinline__ void member_serialize_pipe(const MemSerArgs& a, uint3
 // CU): its jobs are bound by their dependent descriptor loads, and more,
 // shorter job ranges finish sooner (c6 1090 -> 1192 GiB/s), while a dense
 // batch's staging traffic is fastest at 16 waves per CU (C3 447 vs 435 at 24)
-#ifndef DG_MSER_PIPE   // A/B: 0 = round 5's member_serialize
-#define DG_MSER_PIPE 1
-#endif
 __global__ __launch_bounds__(64) void member_serialize_kernel(MemSerArgs a, uint32_t n_jobs, uint32_t staged_grid) {
-#if DG_MSER_PIPE
 	__shared__ __attribute__((aligned(16))) uint8_t vring[2 * kMserVSlot];
 	__shared__ __attribute__((aligned(16))) uint8_t rring[2 * 1024];
 	__shared__ __attribute__((aligned(16))) uint8_t stage[kMserPipeStage + 96];
-#else
-	__shared__ __attribute__((aligned(16))) uint8_t vbuf[kStage + 16];
-	__shared__ __attribute__((aligned(16))) uint8_t stage[kMemSerStage + 96];
-#endif
 	// (uniform for the launch: the scan's total is final before this kernel)
 	const uint64_t dtot = a.v_total ? uni64(a.offsets[a.n_pairs]) : ~0ull;
 	const uint32_t grid = dtot * 2 < a.v_total ? gridDim.x : umin32(gridDim.x, staged_grid);
@@ -1267,11 +1099,7 @@ __global__ __launch_bounds__(64) void member_serialize_kernel(MemSerArgs a, uint
 	const uint32_t j0 = a.job0 + (uint32_t)((uint64_t)n_jobs * blockIdx.x / grid);
 	const uint32_t j1 = a.job0 + (uint32_t)((uint64_t)n_jobs * (blockIdx.x + 1) / grid);
 	if (j0 >= j1) return;
-#if DG_MSER_PIPE
 	member_serialize_pipe(a, j0, j1, vring, rring, stage);
-#else
-	member_serialize(a, j0, j1, vbuf, stage);
-#endif
 }
 
 hipError_t launch_members(const SpecArgs& a, uint32_t n_chunks, uint32_t n_cu, hipStream_t st) {

@@ -3,7 +3,7 @@
 # reads the DG_* measurement switches; the product library reads none and
 # bench.py refuses to print a line with any of them set).
 # Each argument is "ENV=VAL ... -- bench args" (quoted).
-# usage: scripts/ab.sh TAG "DG_FUSED=1 -- --config c2" "-- --config c2" ...
+# usage: scripts/ab.sh TAG "DG_SERIAL_CRC=1 -- --config c2" "-- --config c2" ...
 set -o pipefail
 TAG=$1; shift
 O=gpurun_out

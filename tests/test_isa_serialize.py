@@ -1,14 +1,14 @@
 """ISA check of the serialisers' hand-counted wait.
 
 `serialize_run` (csrc/dg_serialize_wave.h) loads the next tile's records into
-registers by inline asm, and the member serialiser's pipeline (and the A/B
-`serialize_pipe`) load what a later tile needs by LDS-DMA into rings; each
-trusts one `s_waitcnt vmcnt(N)` before the loaded words are used.  VMEM operations complete in
-issue order, so that wait covers the DMAs only if at least N VMEM operations
-were issued after them on every path (or an earlier wait already covered
-them).  A compiler change that merges, splits or adds a VMEM operation there
-would make the records silently wrong; and nothing may read or write a
-register load's destination before the wait covers it.
+registers by inline asm, and the member serialiser's pipeline loads what a
+later tile needs by LDS-DMA into rings; each trusts one `s_waitcnt vmcnt(N)`
+before the loaded words are used.  VMEM operations complete in issue order, so
+that wait covers the DMAs only if at least N VMEM operations were issued after
+them on every path (or an earlier wait already covered them).  A compiler
+change that merges, splits or adds a VMEM operation there would make the
+records silently wrong; and nothing may read or write a register load's
+destination before the wait covers it.
 
 This test disassembles the built gfx950 code object (CPU only, no GPU), finds
 the asm markers (`s_nop 7; s_nop 6` after the DMAs, `s_nop 7; s_nop 4` after
@@ -107,7 +107,7 @@ def _check_kernel(ins, base, raw_lines):
     for i in range(1, len(ins) - 1):
         if not (ins[i][1] == "s_nop" and ins[i][2].startswith("7") and ins[i + 1][1] == "s_nop"):
             continue
-        if ins[i + 1][2].startswith("6"):     # LDS-DMA group (serialize_pipe, member pipeline)
+        if ins[i + 1][2].startswith("6"):     # LDS-DMA group (member pipeline)
             assert any(ins[i - k][1].startswith("global_load_lds") for k in range(1, 6) if i - k >= 0), \
                 f"{ins[i][0]:#x}: DMA marker without a DMA before it"
             groups.append((i + 2, set()))
