@@ -2,7 +2,9 @@
 // lists in and out (src/c/encoding.c:39-178, apply.c:98-115).
 //
 // Pure host code with no HIP dependency, so it is also compiled alone under
-// AddressSanitizer/UBSan with dg_inplace.cpp by tests/test_host_sanitize.py.
+// AddressSanitizer/UBSan with dg_inplace.cpp by tests/test_host_sanitize.py
+// (and with dg_plan.cpp, whose --verbose report decodes deltas here, by
+// tests/test_plan_cpu.py).
 // The device path never comes here: the GPU serializer writes the same bytes
 // from its own records (dg_serialize_wave.h) and the decode kernel parses
 // them itself; these entry points are for callers that work at the

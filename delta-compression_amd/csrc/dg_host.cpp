@@ -1,103 +1,26 @@
 // dg_host.cpp — host side of libdeltagpu.so: the C ABI of include/delta_gpu.h.
 //
-// Thin by design: it sizes tables (onepass.c:61-62, correcting.c:116-129),
-// lays out device work buffers for a batch, launches the kernels of
-// dg_kernels.hip on one HIP stream, and moves host buffers through pinned
-// staging for the host-memory entry points.  There is no CPU compute
-// fallback: without a GPU every entry point fails with DG_ERR_NO_DEVICE.
+// Thin by design: it validates the arguments, allocates and uploads what
+// dg_plan.cpp computed (the CRC constant tables of a context; the table sizes
+// and buffer geometry of a batch), and enqueues the kernels of the .hip files
+// on the run stream and one side stream.  The host-memory entry points are in
+// dg_host_io.cpp.  There is no CPU compute fallback: without a GPU every
+// entry point fails with DG_ERR_NO_DEVICE.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <map>
 #include <new>
 #include <string>
 #include <vector>
 
 #include "../../include/delta_gpu.h"
 #include "dg_device.h"
+#include "dg_plan.h"
 
 using namespace dg;
-
-// ───────────────────────────── small host math ────────────────────────────
-
-namespace {
-
-typedef unsigned __int128 u128;
-
-uint64_t mulmod64(uint64_t a, uint64_t b, uint64_t m) { return (uint64_t)((u128)a * b % m); }
-
-uint64_t powmod64(uint64_t b, uint64_t e, uint64_t m) {
-	uint64_t r = 1 % m;
-	b %= m;
-	for (; e; e >>= 1) {
-		if (e & 1) r = mulmod64(r, b, m);
-		b = mulmod64(b, b, m);
-	}
-	return r;
-}
-
-// Deterministic Miller-Rabin; the first 12 prime bases decide every n < 2^64.
-// (The reference uses 100 time-seeded random bases, src/c/hash.c:163-178.)
-bool is_prime_u64(uint64_t n) {
-	static const uint64_t B[] = {2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37};
-	if (n < 2) return false;
-	for (uint64_t b : B) {
-		if (n == b) return true;
-		if (n % b == 0) return false;
-	}
-	uint64_t d = n - 1;
-	int s = 0;
-	while (!(d & 1)) { d >>= 1; ++s; }
-	for (uint64_t b : B) {
-		uint64_t x = powmod64(b, d, n);
-		if (x == 1 || x == n - 1) continue;
-		bool composite = true;
-		for (int i = 1; i < s && composite; ++i) {
-			x = mulmod64(x, x, n);
-			if (x == n - 1) composite = false;
-		}
-		if (composite) return false;
-	}
-	return true;
-}
-
-// src/c/hash.c:180-190
-uint64_t next_prime(uint64_t n) {
-	if (n <= 2) return 2;
-	uint64_t c = (n % 2 == 0) ? n + 1 : n;
-	while (!is_prime_u64(c)) c += 2;
-	return c;
-}
-
-// ── GF(2)[x] mod P, reflected representation (bit 63 = x^0) ──
-uint64_t gf2_mul(uint64_t a, uint64_t b) {
-	uint64_t p = 0;
-	for (int i = 0; i < 64; ++i) {
-		if ((a >> (63 - i)) & 1) p ^= b;
-		b = (b & 1) ? (b >> 1) ^ kCrcPoly : (b >> 1);
-	}
-	return p;
-}
-
-uint64_t gf2_xpow(uint64_t n) {   // x^n mod P
-	uint64_t r = 1ULL << 63, base = 1ULL << 62;
-	for (; n; n >>= 1) {
-		if (n & 1) r = gf2_mul(r, base);
-		base = gf2_mul(base, base);
-	}
-	return r;
-}
-
-uint64_t gf2_div_x(uint64_t z) {   // z * x^-1 mod P
-	const uint64_t l = z >> 63;   // bit 63 of z*... equals the lsb shifted out
-	return ((z ^ (l ? kCrcPoly : 0)) << 1) | l;
-}
-
-}  // namespace
 
 // ───────────────────────────── context ────────────────────────────────────
 
@@ -109,6 +32,7 @@ struct dg_context {
 	uint64_t* d_k32 = nullptr;          // x^(8 * 32 * t), t = 0..1023 (the correcting build's CRC)
 	uint64_t kseg = 0;
 	uint32_t n_cu = 256;                // compute units (grid caps)
+	int lds_bytes = 0;                  // LDS a block may use (0: not known)
 	uint64_t table_pool_bytes = 0;      // DG_LIMIT_TABLE_POOL_BYTES (0 = automatic)
 	uint64_t onepass_members = 0;       // DG_LIMIT_ONEPASS_MEMBERS (0 auto, 1 on, 2 off)
 	uint64_t limits_gen = 0;            // bumped by every dg_context_set_limit (cached plans key on it)
@@ -198,100 +122,19 @@ int dg_context_create(int device, dg_context_t** out) {
 		int cus = 0;
 		if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0)
 			ctx->n_cu = (uint32_t)cus;
+		if (hipDeviceGetAttribute(&ctx->lds_bytes, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess)
+			ctx->lds_bytes = 0;
 	}
 
-	// CRC tables: slicing-by-8 and nibble tables of the combine constants
-	// + the finaliser's constants: x^(8 kCrcSegBytes) and the 16 pad inverses
-	std::vector<uint64_t> tab(kCrcTabWords);
-	for (int i = 0; i < 256; ++i) {
-		uint64_t c = (uint64_t)i;
-		for (int k = 0; k < 8; ++k) c = (c & 1) ? (c >> 1) ^ kCrcPoly : c >> 1;
-		tab[i] = c;
-	}
-	for (int k = 1; k < 8; ++k)
-		for (int i = 0; i < 256; ++i) {
-			const uint64_t prev = tab[(k - 1) * 256 + i];
-			tab[k * 256 + i] = (prev >> 8) ^ tab[prev & 0xff];
-		}
-	for (int lv = 0; lv < kCrcLevels; ++lv) {
-		const uint64_t K = gf2_xpow(8ull * 1024 << lv);
-		for (int j = 0; j < 16; ++j)
-			for (int nb = 0; nb < 16; ++nb)
-				tab[8 * 256 + lv * kCrcNibTabWords + 16 * j + nb] = gf2_mul(K, (uint64_t)nb << (4 * j));
-	}
-	uint64_t xinv[16];
-	xinv[0] = 1ULL << 63;
-	for (int t = 1; t < 16; ++t) {
-		uint64_t z = xinv[t - 1];
-		for (int b = 0; b < 8; ++b) z = gf2_div_x(z);
-		xinv[t] = z;
-	}
-	ctx->kseg = gf2_xpow(8ull * kCrcSegBytes);
-	for (int c = 0; c < kCrcFinTabs; ++c) {   // nibble tables: kseg, xinv[0..15], kseg^2..4, x^(8*256|512|48Ki)
-		const uint64_t K = c == 0 ? ctx->kseg
-		                 : c <= 16 ? xinv[c - 1]
-		                 : c <= 19 ? gf2_xpow(8ull * kCrcSegBytes * (uint64_t)(c - 15))
-		                 : c == kCrcFinX256 ? gf2_xpow(8ull * 256)
-		                 : c == kCrcFinX512 ? gf2_xpow(8ull * 512) : gf2_xpow(8ull * 48 * 1024);
-		for (int j = 0; j < 16; ++j)
-			for (int nb = 0; nb < 16; ++nb)
-				tab[8 * 256 + (kCrcLevels + c) * kCrcNibTabWords + 16 * j + nb] = gf2_mul(K, (uint64_t)nb << (4 * j));
-	}
-	{
-		// row-interleaved segment tables: byte j of a PB-byte piece followed by
-		// the 64 PB - PB bytes of the other lanes' pieces of its row
-		std::vector<uint64_t> adv(256);
-		for (int i = 0; i < 256; ++i) adv[i] = tab[i];   // T advanced by 0 bytes
-		for (int n = 1; n <= 1023; ++n) {
-			for (int i = 0; i < 256; ++i) adv[i] = (adv[i] >> 8) ^ tab[adv[i] & 0xff];
-			if (n >= 1008)   // n = 1023 - j
-				for (int i = 0; i < 256; ++i) tab[kCrcRows16 + (1023 - n) * 256 + i] = adv[i];
-			if (n >= 504 && n <= 511)   // n = 511 - j
-				for (int i = 0; i < 256; ++i) tab[kCrcRows8 + (511 - n) * 256 + i] = adv[i];
-		}
-		uint64_t z = 1ULL << 63;   // x^0
-		for (int l = 0; l < 64; ++l) {   // x^(-8*16*l), x^(-8*8*l)
-			tab[kCrcRowK16 + l] = z;
-			for (int b = 0; b < 128; ++b) z = gf2_div_x(z);
-		}
-		z = 1ULL << 63;
-		for (int l = 0; l < 64; ++l) {
-			tab[kCrcRowK8 + l] = z;
-			for (int b = 0; b < 64; ++b) z = gf2_div_x(z);
-		}
-		// five-bit row tables: the images Z^n(2^i) of the 64 register bits
-		// (Z = one zero byte through the register), combined per 5-bit field
-		auto five = [&](uint32_t base, int n) {
-			uint64_t col[64];
-			for (int i = 0; i < 64; ++i) {
-				uint64_t x = 1ULL << i;
-				for (int k = 0; k < n; ++k) x = (x >> 8) ^ tab[x & 0xff];
-				col[i] = x;
-			}
-			for (int k = 0; k < 13; ++k)
-				for (int v = 0; v < 32; ++v) {
-					uint64_t r = 0;
-					for (int b = 0; b < 5; ++b)
-						if (((v >> b) & 1) && 5 * k + b < 64) r ^= col[5 * k + b];
-					tab[base + 32 * k + v] = r;
-				}
-		};
-		five(kCrc5R8, 512);
-		five(kCrc5R16, 1024);
-		five(kCrc5R16 + 32 * 13, 1016);
-	}
-	std::vector<uint64_t> k32(1024);
-	{
-		const uint64_t step = gf2_xpow(8ull * 32);
-		k32[0] = 1ULL << 63;
-		for (int t = 1; t < 1024; ++t) k32[t] = gf2_mul(k32[t - 1], step);
-	}
-	if (hipMalloc(&ctx->d_crc_tables, tab.size() * 8) != hipSuccess ||
-	    hipMalloc(&ctx->d_xinv, sizeof xinv) != hipSuccess ||
-	    hipMalloc(&ctx->d_k32, 8 * k32.size()) != hipSuccess ||
-	    hipMemcpy(ctx->d_crc_tables, tab.data(), tab.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
-	    hipMemcpy(ctx->d_xinv, xinv, sizeof xinv, hipMemcpyHostToDevice) != hipSuccess ||
-	    hipMemcpy(ctx->d_k32, k32.data(), 8 * k32.size(), hipMemcpyHostToDevice) != hipSuccess) {
+	CrcTables t;
+	crc_tables_build(t);
+	ctx->kseg = t.kseg;
+	if (hipMalloc(&ctx->d_crc_tables, t.tab.size() * 8) != hipSuccess ||
+	    hipMalloc(&ctx->d_xinv, sizeof t.xinv) != hipSuccess ||
+	    hipMalloc(&ctx->d_k32, sizeof t.k32) != hipSuccess ||
+	    hipMemcpy(ctx->d_crc_tables, t.tab.data(), t.tab.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
+	    hipMemcpy(ctx->d_xinv, t.xinv, sizeof t.xinv, hipMemcpyHostToDevice) != hipSuccess ||
+	    hipMemcpy(ctx->d_k32, t.k32, sizeof t.k32, hipMemcpyHostToDevice) != hipSuccess) {
 		dg_context_destroy(ctx);
 		return DG_ERR_HIP;
 	}
@@ -341,34 +184,9 @@ const char* dg::ab_env(const char* name) {
 #endif
 }
 
-// ───────────────────────────── CRC planning ───────────────────────────────
+// ───────────────────────────── device buffers ─────────────────────────────
 
 namespace {
-
-// Segment layout for spans whose device address is 16-byte aligned at
-// offset 0 of the arena (checked at run time): the padded domain is
-// [align_down(off,16), align_up(off+len,16)).
-// outs: where span i's CRC goes in CrcArgs::out (nullptr: at i)
-void plan_crc_spans(const std::vector<dg_span_t>& spans, const std::vector<uint32_t>& which,
-                    std::vector<CrcSpanDev>& sd, std::vector<CrcSegDev>& seg,
-                    const std::vector<uint32_t>* outs = nullptr) {
-	sd.resize(spans.size());
-	seg.clear();
-	for (size_t i = 0; i < spans.size(); ++i) {
-		CrcSpanDev& s = sd[i];
-		s.off = spans[i].off;
-		s.len = spans[i].len;
-		s.seg_base = (uint32_t)seg.size();
-		s.nseg = 0;
-		s.which = which[i];
-		s.out = outs ? (*outs)[i] : (uint32_t)i;
-		if (s.len >= 8) {
-			const uint64_t a0 = s.off & ~15ull, a1 = (s.off + s.len + 15) & ~15ull;
-			s.nseg = (uint32_t)((a1 - a0 + kCrcSegBytes - 1) / kCrcSegBytes);
-			for (uint32_t j = 0; j < s.nseg; ++j) seg.push_back(CrcSegDev{(uint32_t)i, j});
-		}
-	}
-}
 
 struct DevBuf {
 	void* p = nullptr;
@@ -414,6 +232,58 @@ struct HostWord {
 	uint32_t read() const { return __atomic_load_n(h, __ATOMIC_RELAXED); }
 };
 
+// Stage timing of a plan: `slots` sets of `per_run` events, one set per
+// timed run (a ring); ev holds ev_sets >= slots sets (never shrunk, only the
+// ring is).  The caller has the plan's device current.
+struct TimingRing {
+	std::vector<hipEvent_t> ev;
+	uint32_t per_run = 0;
+	uint32_t slots = 0, runs = 0, ev_sets = 0;
+	uint32_t every = 1, calls = 0;   // events on every `every`-th run (dg_*_plan_set_timing_every)
+	bool timing = false;
+	~TimingRing() {
+		for (auto& e : ev)
+			if (e) hipEventDestroy(e);
+	}
+	// false: an event could not be created (timing is then off)
+	bool set(uint32_t n_slots, uint32_t events_per_run) {
+		if (n_slots > ev_sets) {
+			for (auto& e : ev) hipEventDestroy(e);
+			ev.assign((size_t)events_per_run * n_slots, nullptr);
+			per_run = events_per_run;
+			ev_sets = slots = 0;
+			for (auto& e : ev)
+				// timing only: no system-scope fence when the event is recorded
+				// (a cache writeback + invalidate per event slowed the timed
+				// steps by 15 %: C2 0.335 -> 0.391 ms with two events per step)
+				if (hipEventCreateWithFlags(&e, hipEventDisableSystemFence) != hipSuccess) {
+					e = nullptr;
+					timing = false;
+					return false;
+				}
+			ev_sets = n_slots;
+		}
+		// the ring is exactly `slots` runs long, so stage_times averages the
+		// last `slots` runs even after a longer ring was set before
+		slots = n_slots;
+		timing = n_slots > 0;
+		runs = calls = 0;
+		return true;
+	}
+	void set_every(uint32_t n) {
+		every = n;
+		calls = 0;
+	}
+	// the event set this run records, or nullptr (timing off, or not this run's turn)
+	hipEvent_t* next() {
+		if (!timing || calls++ % every != 0) return nullptr;
+		return &ev[(size_t)per_run * (runs++ % slots)];
+	}
+	// recorded sets to average over, and set s of them
+	uint32_t used() const { return slots ? std::min(runs, slots) : 0; }
+	hipEvent_t* set_at(uint32_t s) { return &ev[(size_t)per_run * s]; }
+};
+
 }  // namespace
 
 // ───────────────────────────── encode plan ────────────────────────────────
@@ -423,35 +293,19 @@ struct dg_encode_plan {
 	dg_algorithm_t algo = DG_ALGO_ONEPASS;
 	dg_diff_options_t opts{};
 	uint32_t n = 0;
-	std::vector<dg_pair_t> pairs;
-	std::vector<PairPlanDev> pp;
-	uint64_t out_bound = 0;
-	uint64_t total_rec = 0;
-	uint64_t qmax = 0;
-	uint64_t ctab_entries = 0;   // correcting: sum of per-pair index sizes
-	uint64_t greedy_heads = 0;   // greedy: sum of per-pair head words (buckets + 1), in d_ctab
-	uint64_t max_seeds = 0;
-	uint32_t n_tables = 0;
-	bool aligned16 = true;   // every pair offset a multiple of 16 (LDS-window kernel)
+	EncodeGeometry g;   // sizes and layout (dg_plan.h); g.members: member mode in use
 	// device buffers
 	DevBuf d_pairs, d_pplan, d_powc, d_rec, d_nrec, d_dsize, d_crc_spans_r, d_crc_segs,
 	    d_seg_crc, d_crc, d_tables, d_locks, d_tags, d_ctab, d_lookback, d_kcls, d_gpairs, d_prio_flag,
 	    d_gent;   // greedy: (offset, tag) per seed of every R
-	uint32_t n_gpairs = 0;       // correcting: pairs whose R index is built in memory
 	// onepass member mode (dg_members.hip): member arrays share the record
 	// slots' indexing; the verification work queue
-	bool members = false;
 	DevBuf d_mem_s, d_srec, d_nmem, d_chunks, d_csum, d_cmap, d_seg, d_nseg;
-	uint32_t n_chunks = 0;
-	uint32_t n_crc_spans = 0, n_crc_segs = 0;
 	// fork/join of the CRC kernels onto a side stream
 	hipStream_t side = nullptr;
 	hipEvent_t ev_fork = nullptr, ev_join = nullptr;
 	bool serial_crc = false;   // DG_SERIAL_CRC=1: CRC on the run stream, before the differencing (A/B bound)
 	bool skip_crc = false;     // DG_SKIP_CRC=1: no CRC kernels, wrong header CRCs (A/B bound only)
-	uint32_t corr_lds_cap = 0; // correcting: R indexes up to this many slots built in LDS (DG_CORR_BUILD=global: none)
-	bool crc_fused = false;    // correcting: R's CRC computed by the LDS build, V's forked after it
-	uint32_t route_min = 0;    // member mode chosen automatically: route poorly verified pairs to the plain chain
 	// automatic member mode: the routed-pair count of the last completed run
 	// (written by scan_sizes_kernel into mapped host memory) decides whether the
 	// routed chain waits for the CRC pass (see the run)
@@ -460,457 +314,97 @@ struct dg_encode_plan {
 	uint32_t plain_streak = 0;   // runs since the last member-mode probe (dg_encode_plan_run)
 	uint64_t member_runs = 0, plain_runs = 0;   // dg_encode_plan_run_modes
 	uint64_t* stats = nullptr; // dg_encode_plan_set_stats: --verbose counters (device, 8 per pair)
-	uint64_t qmin = ~0ull;
-	uint64_t v_total = 0;      // sum |V| of the batch
-	bool fused = false;        // DG_FUSED=1: onepass16 serialises in-kernel (default: scan + serialise)
-	// timing
-	bool timing = false;
 	int timing_mode = DG_TIMING_ALL;
-	// timing: `slots` sets of kTimingEvents events, one set per run (ring);
-	// ev holds ev_sets >= slots sets (never shrunk, only the ring is)
-	std::vector<hipEvent_t> ev;
-	uint32_t slots = 0, runs = 0, ev_sets = 0;
-	uint32_t every = 1, calls = 0;   // events on every `every`-th run (dg_*_plan_set_timing_every)
-	hipEvent_t* cur = nullptr;   // event set of the run being enqueued
+	TimingRing ring;           // kTimingEvents events per run
 };
+
+const PairPlanDev* dg::plan_pp(const dg_encode_plan_t* P) { return P->g.pp.data(); }
 
 static const char* kStageNames[] = {"crc64", "diff", "scan", "serialize+join", "total", "members", "corr_build", "corr_scan"};
 static const char* kGreedyStageNames[] = {"greedy_build", "greedy_scan"};   // stages 6, 7 of a greedy plan
 
-// ── --verbose: the reference's diagnostics from device counters and the delta ──
-
-static uint32_t be32(const uint8_t* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
-
-namespace {
-struct Cmd { bool copy; uint64_t src, dst, len; };
-// the standard delta's commands (encoding.c:39-90 layout), in stream order
-bool parse_cmds(const uint8_t* d, size_t n, std::vector<Cmd>& out) {
-	if (n < 26 || memcmp(d, "DLT\x03", 4) != 0) return false;
-	size_t i = 25;
-	while (i < n) {
-		const uint8_t t = d[i];
-		if (t == 0) return true;
-		if (t == 1 && i + 13 <= n) {
-			out.push_back(Cmd{true, be32(d + i + 1), be32(d + i + 5), be32(d + i + 9)});
-			i += 13;
-		} else if (t == 2 && i + 9 <= n) {
-			const uint64_t len = be32(d + i + 5);
-			out.push_back(Cmd{false, 0, be32(d + i + 1), len});
-			i += 9 + len;
-		} else {
-			return false;
-		}
-	}
-	return false;
-}
-
-// delta_print_command_stats (correcting.c:523-576)
-void print_command_stats(const std::vector<Cmd>& cmds) {
-	uint64_t tc = 0, ta = 0, nc = 0, na = 0;
-	std::vector<uint64_t> lens;
-	for (const Cmd& c : cmds) {
-		if (c.copy) { tc += c.len; ++nc; lens.push_back(c.len); }
-		else { ta += c.len; ++na; }
-	}
-	const uint64_t tot = tc + ta;
-	fprintf(stderr,
-	        "  result: %llu copies (%llu bytes), %llu adds (%llu bytes)\n"
-	        "  result: copy coverage %.1f%%, output %llu bytes\n",
-	        (unsigned long long)nc, (unsigned long long)tc, (unsigned long long)na, (unsigned long long)ta,
-	        tot > 0 ? (double)tc / tot * 100.0 : 0.0, (unsigned long long)tot);
-	if (!lens.empty()) {
-		std::sort(lens.begin(), lens.end());
-		fprintf(stderr, "  copies: %llu regions, min=%llu max=%llu mean=%.1f median=%llu bytes\n",
-		        (unsigned long long)lens.size(), (unsigned long long)lens.front(), (unsigned long long)lens.back(),
-		        (double)tc / lens.size(), (unsigned long long)lens[lens.size() / 2]);
-	}
-}
-}  // namespace
-
-void dg::print_verbose(const dg_encode_plan_t* P, uint32_t i, const uint64_t* st, const uint8_t* delta,
-                       size_t delta_len) {
-	const dg_pair_t& d = P->pairs[i];
-	const PairPlanDev& x = P->pp[i];
-	const uint64_t p = P->opts.p;
-	if (d.v_len == 0) return;   // the reference returns before printing (onepass.c:58, correcting.c:112)
-	std::vector<Cmd> cmds;
-	parse_cmds(delta, delta_len, cmds);
-	if (P->algo == DG_ALGO_ONEPASS) {
-		// onepass.c:64-69 and :277-285.  positions: every epoch's steps up to
-		// its match (t + 1, t = max(v_m - v0, r_m - r0)) plus the final
-		// epoch's steps while either stream has a window; lookups: one per
-		// match (a probe counts only on a full-fingerprint hit, onepass.c:169-
-		// 219, and fingerprints of distinct 16-byte windows coincide with
-		// probability ~2^-61)
-		fprintf(stderr, "onepass: %s, q=%llu, |R|=%llu, |V|=%llu, seed_len=%llu\n", "hash table",
-		        (unsigned long long)x.q, (unsigned long long)d.r_len, (unsigned long long)d.v_len,
-		        (unsigned long long)p);
-		uint64_t pos = 0, matches = 0, v0 = 0, r0 = 0;
-		for (const Cmd& c : cmds) {
-			if (!c.copy) continue;
-			pos += std::max(c.dst - v0, c.src - r0) + 1;
-			++matches;
-			v0 = c.dst + c.len;
-			r0 = c.src + c.len;
-		}
-		const uint64_t nv = d.v_len + 1 >= v0 + p ? d.v_len + 1 - p - v0 : 0;
-		const uint64_t nr = d.r_len + 1 >= r0 + p ? d.r_len + 1 - p - r0 : 0;
-		pos += std::max(nv, nr);
-		fprintf(stderr,
-		        "  scan: %llu positions, %llu lookups, %llu matches (flushes)\n"
-		        "  scan: hit rate %.1f%% (of lookups)\n",
-		        (unsigned long long)pos, (unsigned long long)matches, (unsigned long long)matches,
-		        matches > 0 ? 100.0 : 0.0);
-		print_command_stats(cmds);
-		return;
-	}
-	if (P->algo == DG_ALGO_GREEDY) {   // greedy.c:146-150, 255-257
-		fprintf(stderr, "greedy: %s, |R|=%llu, |V|=%llu, seed_len=%llu\n",
-		        ((P->opts.flags >> DG_OPT_SPLAY) & 1) ? "splay tree" : "hash table", (unsigned long long)d.r_len,
-		        (unsigned long long)d.v_len, (unsigned long long)p);
-		print_command_stats(cmds);
-		return;
-	}
-	// correcting.c:137-152, 200-214, 470-485
-	const uint64_t seeds = d.r_len >= p ? d.r_len - p + 1 : 0;
-	const uint64_t cap = x.q, m = x.m, k = st ? st[6] : 0;
-	const uint64_t expected = m > 0 ? seeds / m : 0;
-	fprintf(stderr,
-	        "correcting: %s, |C|=%llu |F|=%llu m=%llu k=%llu\n"
-	        "  checkpoint gap=%llu bytes, expected fill ~%llu (~%llu%% table occupancy)\n"
-	        "  table memory ~%llu MB\n",
-	        "hash table", (unsigned long long)cap, (unsigned long long)x.f_size, (unsigned long long)m,
-	        (unsigned long long)k, (unsigned long long)m, (unsigned long long)expected,
-	        (unsigned long long)(cap > 0 ? expected * 100 / cap : 0), (unsigned long long)(cap * 24 / 1048576));
-	const uint64_t passed = st ? st[0] : 0, stored = st ? st[1] : 0, in_cap = st ? st[7] : 0;
-	fprintf(stderr,
-	        "  build: %llu seeds, %llu passed checkpoint (%.2f%%), %llu stored, %llu collisions\n"
-	        "  build: table occupancy %llu/%llu (%.1f%%)\n",
-	        (unsigned long long)seeds, (unsigned long long)passed, seeds > 0 ? (double)passed / seeds * 100.0 : 0.0,
-	        (unsigned long long)stored, (unsigned long long)(in_cap - stored), (unsigned long long)stored,
-	        (unsigned long long)cap, cap > 0 ? (double)stored / cap * 100.0 : 0.0);
-	const uint64_t vseeds = d.v_len >= p ? d.v_len - p + 1 : 0;
-	const uint64_t ck = st ? st[2] : 0, fpm = st ? st[3] : 0, bm = st ? st[4] : 0, mt = st ? st[5] : 0;
-	fprintf(stderr,
-	        "  scan: %llu V positions, %llu checkpoints (%.3f%%), %llu matches\n"
-	        "  scan: hit rate %.1f%% (of checkpoints), fp collisions %llu, byte mismatches %llu\n",
-	        (unsigned long long)vseeds, (unsigned long long)ck, vseeds > 0 ? (double)ck / vseeds * 100.0 : 0.0,
-	        (unsigned long long)mt, ck > 0 ? (double)mt / ck * 100.0 : 0.0, (unsigned long long)fpm,
-	        (unsigned long long)bm);
-	print_command_stats(cmds);
-}
-
 extern "C" {
 
-// member mode wanted for this batch (automatic choice by mean pair size:
-// measured C3 (256 KiB pairs) +56 %, C2 (64 KiB pairs) -22 %,
-// profiles/r02_experiments.md); the context's mode and the A/B switches
-// DG_NO_MEMBERS / DG_MEMBERS override it
-static bool members_wanted(const dg_context_t* ctx, const dg_pair_t* pairs, uint32_t n) {
-	uint64_t vsum = 0;
-	for (uint32_t i = 0; i < n; ++i) vsum += pairs[i].v_len;
-	bool want = n && vsum / n >= (128u << 10);
-	if (ctx->onepass_members == 1) want = true;
-	if (ctx->onepass_members == 2) want = false;
-	const char* nm = ab_env("DG_NO_MEMBERS");
-	if (nm && nm[0] == '1') want = false;
-	const char* fm = ab_env("DG_MEMBERS");
-	if (fm && fm[0] == '1') want = true;
-	return want;
-}
 #ifndef DG_CRC_PRIO_FLAG   // A/B: member plans raise the rows pass to priority 1 after the member kernel
 #define DG_CRC_PRIO_FLAG 0
 #endif
 constexpr bool kCrcPrioFlag = DG_CRC_PRIO_FLAG != 0;
 
-int dg_encode_plan_create(dg_context_t* ctx, dg_algorithm_t algo, const dg_pair_t* pairs,
-                          uint32_t n, const dg_diff_options_t* opts, dg_encode_plan_t** out) {
-	*out = nullptr;
-	if (!ctx) return DG_ERR_INVALID_ARG;
-	dg_diff_options_t o;
-	if (opts) o = *opts; else dg_diff_options_default(&o);
-	if (algo != DG_ALGO_GREEDY && algo != DG_ALGO_ONEPASS && algo != DG_ALGO_CORRECTING)
-		return set_err(ctx, DG_ERR_INVALID_ARG, "unknown algorithm %d", (int)algo);
-	// greedy: --splay only picks the smallest offset among the longest matches
-	// (greedy.c:174-195); for the other two it changes which seeds are kept
-	if (((o.flags >> DG_OPT_SPLAY) & 1) && algo != DG_ALGO_GREEDY)
-		return set_err(ctx, DG_ERR_UNSUPPORTED, "--splay is not supported (hash-table path only)");
-	if ((o.flags >> DG_OPT_INPLACE) & 1)
-		return set_err(ctx, DG_ERR_UNSUPPORTED,
-		               "in-place conversion is a host step: encode standard deltas, then dg_make_inplace");
-	if (o.p == 0) return set_err(ctx, DG_ERR_INVALID_ARG, "--seed-len must be >= 1");
-	if (o.p > 65536) return set_err(ctx, DG_ERR_INVALID_ARG, "--seed-len above 65536 is not supported");
-	if (algo == DG_ALGO_CORRECTING && o.buf_cap > 4095)
-		return set_err(ctx, DG_ERR_UNSUPPORTED, "--buffer-size above 4095 is not supported (LDS lookback ring)");
-	if (n > 0 && !pairs) return DG_ERR_INVALID_ARG;
-
-	dg_encode_plan_t* P = new (std::nothrow) dg_encode_plan_t();
-	if (!P) return DG_ERR_NOMEM;
-	P->ctx = ctx;
-	P->algo = algo;
-	P->opts = o;
-	P->n = n;
-	P->pairs.assign(pairs, pairs + n);
-	P->pp.resize(n);
+// geometry -> allocations -> uploads -> side stream and events; on failure the
+// caller destroys the half-built plan
+static int plan_fill(dg_encode_plan_t* P, const dg_pair_t* pairs) {
+	dg_context_t* ctx = P->ctx;
+	const dg_algorithm_t algo = P->algo;
+	const uint32_t n = P->n;
+	EncodeGeometry& g = P->g;
+	PlanEnv env;
+	env.n_cu = ctx->n_cu;
+	env.lds_bytes = ctx->lds_bytes;
+	env.table_pool_bytes = ctx->table_pool_bytes;
+	env.onepass_members = ctx->onepass_members;
+	env.onepass16 = onepass16_selected();
+	env.no_members = ab_env("DG_NO_MEMBERS");
+	env.members = ab_env("DG_MEMBERS");
+	env.corr_build = ab_env("DG_CORR_BUILD");
+	env.fused = ab_env("DG_FUSED");
+	env.route_min = ab_env("DG_ROUTE_MIN");
+	std::string err;
+	const int rc = encode_geometry(algo, P->opts, pairs, n, env, g, err);
+	if (rc != DG_OK) {
+		if (!err.empty()) ctx->err = err;
+		return rc;
+	}
 	hipSetDevice(ctx->device);
 
-	std::map<uint64_t, uint64_t> qcache;
-	uint64_t rec = 0, bound = 0, ctab = 0, gents = 0;
-	const uint64_t p = o.p;
-	for (uint32_t i = 0; i < n; ++i) {
-		const dg_pair_t& d = pairs[i];
-		// the format's u32 fields cap every buffer below 4 GiB (encoding.c:63,72-78);
-		// the kernels keep 32-bit cursors with 1 MiB of headroom
-		if (d.r_len >= (1ull << 32) - (1ull << 20) || d.v_len >= (1ull << 32) - (1ull << 20)) {
-			delete P;
-			return set_err(ctx, DG_ERR_TOO_LARGE, "pair %u: buffers of 4 GiB or more do not fit the u32 format", i);
-		}
-		if ((d.r_off | d.v_off) & 15) P->aligned16 = false;
-		PairPlanDev& x = P->pp[i];
-		memset(&x, 0, sizeof x);
-		const uint64_t seeds = d.r_len >= p ? d.r_len - p + 1 : 0;
-		if (algo == DG_ALGO_ONEPASS) {
-			const uint64_t want = std::max<uint64_t>(o.q, seeds / p);   // onepass.c:61-62
-			auto it = qcache.find(want);
-			x.q = it != qcache.end() ? it->second : (qcache[want] = next_prime(want));
-		} else if (algo == DG_ALGO_GREEDY) {
-			// the seed index (dg_greedy.hip): a power-of-two bucket count >= the
-			// seed count, heads[buckets + 1] and one entry per seed;
-			// --table-size and --max-table do not apply (q stays 0)
-			uint64_t nb = 1;
-			while (nb < seeds) nb <<= 1;
-			x.f_size = nb;
-			x.tab_base = ctab;
-			x.m = gents;
-			ctab += nb + 1;
-			gents += seeds;
-			P->max_seeds = std::max<uint64_t>(P->max_seeds, seeds);
-		} else {
-			// correcting.c:116-129
-			const uint64_t mt = o.max_table > 0 ? o.max_table : DG_MAX_TABLE_SIZE;
-			uint64_t raw = seeds > 0 ? std::max<uint64_t>(o.q, 2 * seeds / p) : o.q;
-			raw = std::min<uint64_t>(raw, mt);
-			auto it = qcache.find(raw);
-			x.q = it != qcache.end() ? it->second : (qcache[raw] = next_prime(raw));
-			x.f_size = seeds > 0 ? next_prime(2 * seeds) : 1;
-			x.m = x.f_size <= x.q ? 1 : (x.f_size + x.q - 1) / x.q;
-			x.f_magic = UINT64_MAX / x.f_size;
-			x.m_magic = UINT64_MAX / x.m;
-			x.tab_base = ctab;
-			ctab += x.q;
-			P->max_seeds = std::max<uint64_t>(P->max_seeds, seeds);
-		}
-		if (x.q >= 0xFFFFFFFFull) {
-			delete P;
-			return set_err(ctx, DG_ERR_TOO_LARGE, "table size %llu too large", (unsigned long long)x.q);
-		}
-		x.q_magic = x.q ? UINT64_MAX / x.q : 0;
-		x.rec_base = rec;
-		x.rec_cap = (uint32_t)(d.v_len / p + 1);
-		rec += x.rec_cap;
-		// onepass: every COPY covers >= p bytes, so
-		//   delta <= 35 + |V| + (|V|/p) * max(0, 22 - p);
-		// correcting: a tail-corrected COPY may be shorter than p, but there
-		// are at most |V|/p + 1 of them, each with at most one ADD header
-		// (greedy: as onepass)
-		if (algo != DG_ALGO_CORRECTING)
-			bound += 35 + d.v_len + (d.v_len / p) * (p < 22 ? 22 - p : 0);
-		else
-			bound += 57 + d.v_len + 22 * (d.v_len / p);
-		P->qmax = std::max<uint64_t>(P->qmax, x.q);
-		P->qmin = std::min<uint64_t>(P->qmin, x.q);
-	}
-	P->out_bound = bound;
-	P->total_rec = rec;
-	P->ctab_entries = ctab;
-	if (algo == DG_ALGO_GREEDY) {
-		P->greedy_heads = ctab;
-		if (ctab * 4 + gents * 8 > (64ull << 30)) {
-			delete P;
-			return set_err(ctx, DG_ERR_NOMEM, "greedy seed indexes need %llu GiB (limit 64)",
-			               (unsigned long long)((ctab * 4 + gents * 8) >> 30));
-		}
-	} else if (ctab * 4 > (64ull << 30)) {
-		delete P;
-		return set_err(ctx, DG_ERR_NOMEM, "correcting R indexes need %llu GiB (limit 64)",
-		               (unsigned long long)(ctab >> 28));
-	}
-
-	// constants 263^(p-1-k) mod (2^61-1)
-	std::vector<uint64_t> powc(p);
-	{
-		uint64_t c = 1;
-		for (uint64_t k = 0; k < p; ++k) {
-			powc[p - 1 - k] = c;
-			c = (uint64_t)((u128)c * kBase % kMersenne);
-		}
-	}
-	{
-		const char* cb = ab_env("DG_CORR_BUILD");
-		int shm = 0;
-		if (hipDeviceGetAttribute(&shm, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device) != hipSuccess)
-			shm = 0;
-		// Correcting plans compute the CRCs in one of two ways:
-		//   fused   where some R index fits LDS: the LDS build computes R's CRC
-		//           from the bytes it holds and V's runs beside the V scan (C4:
-		//           2.77 ms per step);
-		//   beside  otherwise, the onepass arrangement: both CRCs on the side
-		//           stream beside the build.
-		// One block's LDS less the 2 KiB roll table, the fused R CRC's tables
-		// (10 KiB) and reduction words, and some slack
-		const int fixed = 2048 + 10240 + 128 + 256;
-		if (algo == DG_ALGO_CORRECTING && !(cb && strcmp(cb, "global") == 0) && shm > fixed + 4096)
-			P->corr_lds_cap = (uint32_t)((shm - fixed) / 4);
-		// fused: only R indexes built in LDS compute R's CRC; the others' R
-		// CRCs run in V's pass
-		P->crc_fused = P->corr_lds_cap && P->qmin <= P->corr_lds_cap;
-	}
-	if (P->crc_fused) {   // x^(-8 pad) of each R's zero padding to a multiple of 32 KiB
-		uint64_t xm8 = 1ULL << 63;
-		for (int b = 0; b < 8; ++b) xm8 = gf2_div_x(xm8);
-		std::map<uint64_t, uint64_t> cache;
-		for (uint32_t i = 0; i < n; ++i) {
-			const uint64_t pad = (32768 - pairs[i].r_len % 32768) % 32768;
-			auto it = cache.find(pad);
-			if (it == cache.end()) {
-				uint64_t r = 1ULL << 63, base = xm8;
-				for (uint64_t e = pad; e; e >>= 1) {
-					if (e & 1) r = gf2_mul(r, base);
-					base = gf2_mul(base, base);
-				}
-				it = cache.emplace(pad, r).first;
-			}
-			P->pp[i].crc_unpad = it->second;
-		}
-	}
-	// CRC spans: 2 per pair (R then V; V only when the build computes R's);
-	// arena offsets are rebased at run time
-	std::vector<dg_span_t> spans;
-	std::vector<uint32_t> which, outs;
-	for (uint32_t i = 0; i < n; ++i) {
-		if (!P->crc_fused || P->pp[i].q > P->corr_lds_cap) {
-			spans.push_back(dg_span_t{pairs[i].r_off, pairs[i].r_len});
-			which.push_back(0);
-			outs.push_back(2 * i);
-		}
-		spans.push_back(dg_span_t{pairs[i].v_off, pairs[i].v_len});
-		which.push_back(1);
-		outs.push_back(2 * i + 1);
-	}
-	std::vector<CrcSpanDev> sd;
-	std::vector<CrcSegDev> seg;
-	plan_crc_spans(spans, which, sd, seg, &outs);
-	P->n_crc_spans = (uint32_t)sd.size();
-	P->n_crc_segs = (uint32_t)seg.size();
-
-	// table-tier pool: 2 x qmax u64 per table.  Automatic size: one table per
-	// resident onepass wave (CUs x 4 SIMDs x 5 waves) where that fits in
-	// 4 GiB, at least 1 GiB; never more tables than pairs.
-	const uint64_t per = 16ull * std::max<uint64_t>(P->qmax, 1);
-	uint64_t pool = ctx->table_pool_bytes;
-	if (pool == 0) {
-		const uint64_t resident = 20ull * ctx->n_cu;
-		pool = std::max<uint64_t>(1ull << 30, std::min<uint64_t>(resident * per, 4ull << 30));
-	}
-	P->n_tables = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::max<uint32_t>(n, 1), pool / per));
-	// the device partitions the pool by XCD (8 per GPU): a multiple of 8
-	// tables, at least 8 where the pool holds them
-	if (pool / per >= 8) P->n_tables = std::max<uint32_t>(8, P->n_tables & ~7u);
-
+	const uint32_t n1 = std::max<uint32_t>(n, 1);
+	const size_t p = P->opts.p;
 	int bad = 0;
-	bad |= P->d_pairs.alloc(sizeof(PairDev) * std::max<uint32_t>(n, 1));
-	bad |= P->d_pplan.alloc(sizeof(PairPlanDev) * std::max<uint32_t>(n, 1));
+	bad |= P->d_pairs.alloc(sizeof(PairDev) * n1);
+	bad |= P->d_pplan.alloc(sizeof(PairPlanDev) * n1);
 	bad |= P->d_powc.alloc(8 * p);
 	bad |= P->d_rec.alloc(4ull * (algo != DG_ALGO_CORRECTING ? kRecWordsOnepass : kRecWordsCorrecting) *
-	                      std::max<uint64_t>(rec, 1));
-	bad |= P->d_nrec.alloc(4ull * std::max<uint32_t>(n, 1));
-	bad |= P->d_dsize.alloc(8ull * std::max<uint32_t>(n, 1));
-	bad |= P->d_crc_spans_r.alloc(sizeof(CrcSpanDev) * std::max<size_t>(sd.size(), 1));
-	bad |= P->d_crc_segs.alloc(sizeof(CrcSegDev) * std::max<size_t>(seg.size(), 1));
-	bad |= P->d_seg_crc.alloc(8 * std::max<size_t>(seg.size(), 1));
-	bad |= P->d_crc.alloc(16ull * std::max<uint32_t>(n, 1));   // per pair: CRC of R, of V
-	bad |= P->d_tables.alloc(per * P->n_tables);
-	bad |= P->d_locks.alloc(4ull * P->n_tables);
-	bad |= P->d_tags.alloc(4ull * P->n_tables);
+	                      std::max<uint64_t>(g.total_rec, 1));
+	bad |= P->d_nrec.alloc(4ull * n1);
+	bad |= P->d_dsize.alloc(8ull * n1);
+	bad |= P->d_crc_spans_r.alloc(sizeof(CrcSpanDev) * std::max<size_t>(g.spans.size(), 1));
+	bad |= P->d_crc_segs.alloc(sizeof(CrcSegDev) * std::max<size_t>(g.segs.size(), 1));
+	bad |= P->d_seg_crc.alloc(8 * std::max<size_t>(g.segs.size(), 1));
+	bad |= P->d_crc.alloc(16ull * n1);   // per pair: CRC of R, of V
+	bad |= P->d_tables.alloc(g.table_bytes * g.n_tables);
+	bad |= P->d_locks.alloc(4ull * g.n_tables);
+	bad |= P->d_tags.alloc(4ull * g.n_tables);
 	if (algo == DG_ALGO_CORRECTING) {
-		std::vector<uint32_t> gp;
-		for (uint32_t i = 0; i < n; ++i)
-			if (P->pp[i].q > P->corr_lds_cap) gp.push_back(i);
-		P->n_gpairs = (uint32_t)gp.size();
-		bad |= P->d_gpairs.alloc(4ull * std::max<size_t>(gp.size(), 1));
-		if (!bad && !gp.empty() &&
-		    hipMemcpy(P->d_gpairs.p, gp.data(), 4 * gp.size(), hipMemcpyHostToDevice) != hipSuccess)
+		bad |= P->d_gpairs.alloc(4ull * std::max<size_t>(g.gpairs.size(), 1));
+		if (!bad && !g.gpairs.empty() &&
+		    hipMemcpy(P->d_gpairs.p, g.gpairs.data(), 4 * g.gpairs.size(), hipMemcpyHostToDevice) != hipSuccess)
 			bad = 1;
-		bad |= P->d_ctab.alloc(4ull * std::max<uint64_t>(ctab, 1));
-		bad |= P->d_kcls.alloc(8ull * std::max<uint32_t>(n, 1));
+		bad |= P->d_ctab.alloc(4ull * std::max<uint64_t>(g.ctab_entries, 1));
+		bad |= P->d_kcls.alloc(8ull * n1);
 	}
-	{
-		// DG_FUSED=1: onepass16 serialises in-kernel behind a decoupled look-back.
-		// Off by default: the look-back couples every wave to the slowest pair
-		// before it, which cost 20-25% at C2/C3 on MI355X (profiles/r01_ab_fused_vs_unfused.txt).
-		const char* fz = ab_env("DG_FUSED");
-		P->fused = algo == DG_ALGO_ONEPASS && o.p == 16 && P->aligned16 && onepass16_selected() &&
-		           fz && fz[0] == '1';
-	}
-	if (P->fused) bad |= P->d_lookback.alloc(8ull * std::max<uint32_t>(n, 1));
+	if (g.fused) bad |= P->d_lookback.alloc(8ull * n1);
 	if (algo == DG_ALGO_GREEDY) {
-		bad |= P->d_ctab.alloc(4ull * std::max<uint64_t>(ctab, 1));
-		bad |= P->d_gent.alloc(8ull * std::max<uint64_t>(gents, 1));
+		bad |= P->d_ctab.alloc(4ull * std::max<uint64_t>(g.greedy_heads, 1));
+		bad |= P->d_gent.alloc(8ull * std::max<uint64_t>(g.greedy_entries, 1));
 	}
-	{
-		// member mode: p = 16 onepass over 16-byte aligned pairs (the LDS-window
-		// chain), i.e. the batched hot configuration; DG_NO_MEMBERS=1 (A/B
-		// builds) runs the plain chain
-		// automatic choice by mean pair size for now: measured
-		// (profiles/r02_experiments.md) C3 (256 KiB pairs) +56 %, C2 (64 KiB
-		// pairs, where the plain chain's latency-bound waves overlap the CRC)
-		// -22 %
-		const bool want = members_wanted(ctx, pairs, n);
-		P->members = algo == DG_ALGO_ONEPASS && o.p == 16 && P->aligned16 && onepass16_selected() &&
-		             !P->fused && want;
-		// automatic mode: a pair averaging fewer than 2 verified members per
-		// 2 KiB chunk runs the plain chain (C3: ~39; shift and transposition
-		// pairs, whose matches leave diagonal 0: ~0); forced member mode
-		// keeps every pair on the member chain
-		const char* rm = ab_env("DG_ROUTE_MIN");
-		P->route_min = ctx->onepass_members == 0 ? (rm ? (uint32_t)strtoul(rm, nullptr, 0) : 2u) : 0u;
-	}
-	for (uint32_t i = 0; i < n; ++i) P->v_total += pairs[i].v_len;
-	if (P->members) {
-		// chunks of kMemChunk positions covering [0, min(|R|, |V|)]; member
-		// slots per chunk; the (pair, chunk) table the member kernel's waves index
-		std::vector<uint32_t> jobs;
-		uint64_t slots = 0;
-		for (uint32_t i = 0; i < n; ++i) {
-			const uint64_t E = std::min<uint64_t>(pairs[i].r_len, pairs[i].v_len);
-			const uint32_t nch = (uint32_t)(E / kMemChunk + 1);
-			P->pp[i].mem_base = slots;
-			P->pp[i].chunk_base = P->n_chunks;
-			P->pp[i].n_chunks = nch;
-			for (uint32_t c = 0; c < nch; ++c) {
-				jobs.push_back(i);
-				jobs.push_back(c);
-			}
-			slots += (uint64_t)nch * kMemChunkSlots;
-			P->n_chunks += nch;
-		}
+	if (g.members) {
+		const uint32_t nc1 = std::max<uint32_t>(g.n_chunks, 1);
 		int mbad = 0;
-		mbad |= P->d_mem_s.alloc(4ull * std::max<uint64_t>(slots, 1));
-		mbad |= P->d_srec.alloc(16ull * std::max<uint64_t>(slots, 1));
-		mbad |= P->d_nmem.alloc(4ull * std::max<uint32_t>(P->n_chunks, 1));
-		mbad |= P->d_chunks.alloc(8ull * std::max<uint32_t>(P->n_chunks, 1));
-		mbad |= P->d_csum.alloc(8ull * std::max<uint32_t>(P->n_chunks, 1));
-		mbad |= P->d_cmap.alloc(8ull * std::max<uint32_t>(P->n_chunks, 1));
-		mbad |= P->d_seg.alloc(16ull * ((uint64_t)P->n_chunks + 2ull * n));
-		mbad |= P->d_nseg.alloc(4ull * std::max<uint32_t>(n, 1));
+		mbad |= P->d_mem_s.alloc(4ull * std::max<uint64_t>(g.mem_slots, 1));
+		mbad |= P->d_srec.alloc(16ull * std::max<uint64_t>(g.mem_slots, 1));
+		mbad |= P->d_nmem.alloc(4ull * nc1);
+		mbad |= P->d_chunks.alloc(8ull * nc1);
+		mbad |= P->d_csum.alloc(8ull * nc1);
+		mbad |= P->d_cmap.alloc(8ull * nc1);
+		mbad |= P->d_seg.alloc(16ull * ((uint64_t)g.n_chunks + 2ull * n));
+		mbad |= P->d_nseg.alloc(4ull * n1);
 		mbad |= P->d_prio_flag.alloc(4);
-		if (P->route_min) {
+		if (g.route_min) {
 			mbad |= P->d_route_cnt.alloc(4);
 			mbad |= P->route_fb.alloc();
 			if (!mbad && hipMemset(P->d_route_cnt.p, 0, 4) != hipSuccess) mbad = 1;
 		}
-		if (!mbad && !jobs.empty() &&
-		    hipMemcpy(P->d_chunks.p, jobs.data(), 4 * jobs.size(), hipMemcpyHostToDevice) != hipSuccess)
+		if (!mbad && !g.jobs.empty() &&
+		    hipMemcpy(P->d_chunks.p, g.jobs.data(), 4 * g.jobs.size(), hipMemcpyHostToDevice) != hipSuccess)
 			mbad = 1;
 		if (mbad && ctx->onepass_members != 1) {
 			// automatic mode: member mode is an optimisation, so a batch that
@@ -920,33 +414,27 @@ int dg_encode_plan_create(dg_context_t* ctx, dg_algorithm_t algo, const dg_pair_
 			                  &P->d_seg, &P->d_nseg, &P->d_prio_flag, &P->d_route_cnt})
 				b->release();
 			P->route_fb.release();
-			P->members = false;
-			P->n_chunks = 0;
+			g.members = false;
+			g.n_chunks = 0;
 			mbad = 0;
 		}
 		bad |= mbad;
 	}
-	if (bad) {
-		delete P;
-		return set_err(ctx, DG_ERR_NOMEM, "device allocation failed");
-	}
+	if (bad) return set_err(ctx, DG_ERR_NOMEM, "device allocation failed");
 	hipStream_t st = ctx->stream;
 	hipError_t e = hipSuccess;
 	if (n) {
 		e = hipMemcpyAsync(P->d_pairs.p, pairs, sizeof(PairDev) * n, hipMemcpyHostToDevice, st);
-		if (e == hipSuccess) e = hipMemcpyAsync(P->d_pplan.p, P->pp.data(), sizeof(PairPlanDev) * n, hipMemcpyHostToDevice, st);
-		if (e == hipSuccess) e = hipMemcpyAsync(P->d_crc_spans_r.p, sd.data(), sizeof(CrcSpanDev) * sd.size(), hipMemcpyHostToDevice, st);
-		if (e == hipSuccess && !seg.empty()) e = hipMemcpyAsync(P->d_crc_segs.p, seg.data(), sizeof(CrcSegDev) * seg.size(), hipMemcpyHostToDevice, st);
+		if (e == hipSuccess) e = hipMemcpyAsync(P->d_pplan.p, g.pp.data(), sizeof(PairPlanDev) * n, hipMemcpyHostToDevice, st);
+		if (e == hipSuccess) e = hipMemcpyAsync(P->d_crc_spans_r.p, g.spans.data(), sizeof(CrcSpanDev) * g.spans.size(), hipMemcpyHostToDevice, st);
+		if (e == hipSuccess && !g.segs.empty()) e = hipMemcpyAsync(P->d_crc_segs.p, g.segs.data(), sizeof(CrcSegDev) * g.segs.size(), hipMemcpyHostToDevice, st);
 	}
-	if (e == hipSuccess) e = hipMemcpyAsync(P->d_powc.p, powc.data(), 8 * p, hipMemcpyHostToDevice, st);
+	if (e == hipSuccess) e = hipMemcpyAsync(P->d_powc.p, g.powc.data(), 8 * p, hipMemcpyHostToDevice, st);
 	if (e == hipSuccess) e = hipMemsetAsync(P->d_tables.p, 0, P->d_tables.n, st);
 	if (e == hipSuccess) e = hipMemsetAsync(P->d_locks.p, 0, P->d_locks.n, st);
 	if (e == hipSuccess) e = hipMemsetAsync(P->d_tags.p, 0, P->d_tags.n, st);
 	if (e == hipSuccess) e = hipStreamSynchronize(st);
-	if (e != hipSuccess) {
-		delete P;
-		return set_err(ctx, DG_ERR_HIP, "plan upload failed: %s", hipGetErrorString(e));
-	}
+	if (e != hipSuccess) return set_err(ctx, DG_ERR_HIP, "plan upload failed: %s", hipGetErrorString(e));
 	const char* sc = ab_env("DG_SERIAL_CRC");
 	P->serial_crc = sc && sc[0] == '1';
 	const char* sk = ab_env("DG_SKIP_CRC");
@@ -958,18 +446,33 @@ int dg_encode_plan_create(dg_context_t* ctx, dg_algorithm_t algo, const dg_pair_
 		// default system-scope one writes back and invalidates the caches)
 		if (e == hipSuccess) e = hipEventCreateWithFlags(&P->ev_fork, hipEventDisableTiming | hipEventReleaseToDevice);
 		if (e == hipSuccess) e = hipEventCreateWithFlags(&P->ev_join, hipEventDisableTiming | hipEventReleaseToDevice);
-		if (e != hipSuccess) {
-			dg_encode_plan_destroy(P);
-			return set_err(ctx, DG_ERR_HIP, "side stream creation failed: %s", hipGetErrorString(e));
-		}
+		if (e != hipSuccess) return set_err(ctx, DG_ERR_HIP, "side stream creation failed: %s", hipGetErrorString(e));
+	}
+	return DG_OK;
+}
+
+int dg_encode_plan_create(dg_context_t* ctx, dg_algorithm_t algo, const dg_pair_t* pairs,
+                          uint32_t n, const dg_diff_options_t* opts, dg_encode_plan_t** out) {
+	*out = nullptr;
+	if (!ctx) return DG_ERR_INVALID_ARG;
+	dg_encode_plan_t* P = new (std::nothrow) dg_encode_plan_t();
+	if (!P) return DG_ERR_NOMEM;
+	P->ctx = ctx;
+	P->algo = algo;
+	if (opts) P->opts = *opts; else dg_diff_options_default(&P->opts);
+	P->n = n;
+	const int rc = plan_fill(P, pairs);
+	if (rc != DG_OK) {
+		dg_encode_plan_destroy(P);
+		return rc;
 	}
 	*out = P;
 	return DG_OK;
 }
 
-uint64_t dg_encode_plan_output_bound(const dg_encode_plan_t* P) { return P ? P->out_bound : 0; }
+uint64_t dg_encode_plan_output_bound(const dg_encode_plan_t* P) { return P ? P->g.out_bound : 0; }
 uint32_t dg_encode_plan_num_pairs(const dg_encode_plan_t* P) { return P ? P->n : 0; }
-uint32_t dg_encode_plan_flags(const dg_encode_plan_t* P) { return P && P->members ? DG_PLAN_MEMBERS : 0u; }
+uint32_t dg_encode_plan_flags(const dg_encode_plan_t* P) { return P && P->g.members ? DG_PLAN_MEMBERS : 0u; }
 int dg_encode_plan_run_modes(const dg_encode_plan_t* P, uint64_t* member_runs, uint64_t* plain_runs) {
 	if (!P || !member_runs || !plain_runs) return DG_ERR_INVALID_ARG;
 	*member_runs = P->member_runs;
@@ -987,17 +490,17 @@ int dg_encode_plan_set_stats(dg_encode_plan_t* P, uint64_t* d_stats) {
 // (device pointers; scripts/member_debug.py)
 int dg_encode_plan_member_debug(const dg_encode_plan_t* P, void** mem_s, void** srec, void** n_mem,
                                 void** csum, uint32_t* n_chunks) {
-	if (!P || !P->members) return -1;
+	if (!P || !P->g.members) return -1;
 	*mem_s = P->d_mem_s.p;
 	*srec = P->d_srec.p;
 	*n_mem = P->d_nmem.p;
 	*csum = P->d_csum.p;
-	*n_chunks = P->n_chunks;
+	*n_chunks = P->g.n_chunks;
 	return 0;
 }
 #endif
 uint64_t dg_encode_plan_table_size(const dg_encode_plan_t* P, uint32_t i) {
-	return (P && i < P->n) ? P->pp[i].q : 0;
+	return (P && i < P->n) ? P->g.pp[i].q : 0;
 }
 const uint32_t* dg_encode_plan_copy_counts_device(const dg_encode_plan_t* P) {
 	return P ? P->d_nrec.as<uint32_t>() : nullptr;
@@ -1011,7 +514,7 @@ constexpr uint32_t kTimingAll = (1u << kTimingEvents) - 1u;
 // member kernel: the routed plain chain dominates on data off diagonal 0)
 static uint32_t timing_mask(const dg_encode_plan_t* P) {
 	if (P->timing_mode != DG_TIMING_DOMINANT) return kTimingAll;
-	if (P->members) return (1u << 2) | (1u << 6) | (1u << 3);   // the member kernel, then the chains
+	if (P->g.members) return (1u << 2) | (1u << 6) | (1u << 3);   // the member kernel, then the chains
 	if (P->algo != DG_ALGO_ONEPASS) return (1u << 2) | (1u << 7) | (1u << 3);   // build, scan
 	return (1u << 2) | (1u << 3);
 }
@@ -1019,26 +522,7 @@ static uint32_t timing_mask(const dg_encode_plan_t* P) {
 int dg_encode_plan_set_timing(dg_encode_plan_t* P, int slots) {
 	if (!P || slots < 0) return DG_ERR_INVALID_ARG;
 	hipSetDevice(P->ctx->device);
-	if ((uint32_t)slots > P->ev_sets) {
-		for (auto& e : P->ev) hipEventDestroy(e);
-		P->ev.assign((size_t)kTimingEvents * slots, nullptr);
-		P->ev_sets = P->slots = 0;
-		for (auto& e : P->ev)
-			// timing only: no system-scope fence when the event is recorded
-			// (a cache writeback + invalidate per event slowed the timed
-			// steps by 15 %: C2 0.335 -> 0.391 ms with two events per step)
-			if (hipEventCreateWithFlags(&e, hipEventDisableSystemFence) != hipSuccess) {
-				e = nullptr;
-				P->timing = false;
-				return set_err(P->ctx, DG_ERR_HIP, "hipEventCreate failed");
-			}
-		P->ev_sets = (uint32_t)slots;
-	}
-	// the ring is exactly `slots` runs long, so stage_times averages the
-	// last `slots` runs even after a longer ring was set before
-	P->slots = (uint32_t)slots;
-	P->timing = slots > 0;
-	P->runs = P->calls = 0;
+	if (!P->ring.set((uint32_t)slots, kTimingEvents)) return set_err(P->ctx, DG_ERR_HIP, "hipEventCreate failed");
 	return DG_OK;
 }
 
@@ -1051,20 +535,20 @@ int dg_encode_plan_set_timing(dg_encode_plan_t* P, int slots) {
 // (greedy plans: the same two intervals as greedy_build and greedy_scan).
 // Returns the mean over the runs recorded since set_timing (at most `slots`).
 int dg_encode_plan_stage_times(dg_encode_plan_t* P, float* ms, const char** names, int n) {
-	if (!P || !P->slots || !P->runs) return 0;
-	const uint32_t used = std::min(P->runs, P->slots);
+	const uint32_t used = P ? P->ring.used() : 0;
+	if (!used) return 0;
 	const int pairs[8][2] = {{0, 1}, {2, 3}, {3, 4}, {4, 5}, {2, 5}, {2, 6}, {2, 7}, {7, 3}};
 	const uint32_t mask = timing_mask(P);
 	int sel[8], ns = 0;   // the stages whose two events were recorded
 	for (int k = 0; k < 8; ++k) {
 		if (k >= 6 && P->algo == DG_ALGO_ONEPASS) continue;
-		if (k == 5 && P->members == false && mask != kTimingAll) continue;
+		if (k == 5 && P->g.members == false && mask != kTimingAll) continue;
 		if ((mask >> pairs[k][0] & 1) && (mask >> pairs[k][1] & 1)) sel[ns++] = k;
 	}
-	const int last = (mask >> 5) & 1 ? 5 : (P->members && !(mask >> 3 & 1) ? 6 : 3);
+	const int last = (mask >> 5) & 1 ? 5 : (P->g.members && !(mask >> 3 & 1) ? 6 : 3);
 	double acc[8] = {};
 	for (uint32_t s = 0; s < used; ++s) {
-		hipEvent_t* e = &P->ev[(size_t)kTimingEvents * s];
+		hipEvent_t* e = P->ring.set_at(s);
 		if (hipEventSynchronize(e[last]) != hipSuccess) return 0;
 		for (int i = 0; i < ns; ++i) {
 			float t = 0;
@@ -1088,8 +572,7 @@ int dg_encode_plan_set_timing_mode(dg_encode_plan_t* P, int mode) {
 
 int dg_encode_plan_set_timing_every(dg_encode_plan_t* P, int every) {
 	if (!P || every < 1) return DG_ERR_INVALID_ARG;
-	P->every = (uint32_t)every;
-	P->calls = 0;
+	P->ring.set_every((uint32_t)every);
 	return DG_OK;
 }
 
@@ -1110,7 +593,7 @@ static MemSerArgs mem_ser_args(const dg_encode_plan_t* P, const uint8_t* d_ver, 
 	m.out = d_out;
 	m.out_cap = out_cap;
 	m.status = d_status;
-	m.v_total = P->v_total;
+	m.v_total = P->g.v_total;
 	m.n_pairs = P->n;
 	return m;
 }
@@ -1126,7 +609,7 @@ static int enqueue_onepass(dg_encode_plan_t* P, EncodeArgs a, bool mem, hipEvent
                            hipEvent_t routed_after, hipStream_t st) {
 	dg_context_t* ctx = P->ctx;
 	if (!mem) {
-		HIPCHK(ctx, launch_onepass(a, a.p, P->aligned16, st));
+		HIPCHK(ctx, launch_onepass(a, a.p, P->g.aligned16, st));
 		return DG_OK;
 	}
 	SpecArgs m{};
@@ -1144,15 +627,15 @@ static int enqueue_onepass(dg_encode_plan_t* P, EncodeArgs a, bool mem, hipEvent
 	a.cmap = m.cmap;
 	a.seg = P->d_seg.as<uint32_t>();
 	a.nseg = P->d_nseg.as<uint32_t>();
-	a.route_min = P->route_min;
+	a.route_min = P->g.route_min;
 	a.mem_s = m.mem_s;
 	a.n_mem = m.n_mem;
 	a.srec = m.srec;
-	HIPCHK(ctx, launch_members(m, P->n_chunks, ctx->n_cu, st));
+	HIPCHK(ctx, launch_members(m, P->g.n_chunks, ctx->n_cu, st));
 	if (kCrcPrioFlag) HIPCHK(ctx, hipMemsetD32Async(P->d_prio_flag.p, 1, 1, st));   // the rows pass to priority 1
 	if (ev_members) HIPCHK(ctx, hipEventRecord(ev_members, st));
-	if (P->route_min) a.route_cnt = P->d_route_cnt.as<uint32_t>();
-	HIPCHK(ctx, launch_onepass(a, a.p, P->aligned16, st, routed_after));
+	if (P->g.route_min) a.route_cnt = P->d_route_cnt.as<uint32_t>();
+	HIPCHK(ctx, launch_onepass(a, a.p, P->g.aligned16, st, routed_after));
 	return DG_OK;
 }
 
@@ -1166,14 +649,14 @@ static int enqueue_greedy(dg_encode_plan_t* P, const EncodeArgs& a, hipEvent_t e
 	g.n_pairs = P->n;
 	g.p = a.p;
 	g.splay = (uint32_t)((P->opts.flags >> DG_OPT_SPLAY) & 1);
-	g.max_seeds = (uint32_t)P->max_seeds;
+	g.max_seeds = (uint32_t)P->g.max_seeds;
 	g.heads = P->d_ctab.as<uint32_t>();
 	g.ent = P->d_gent.as<uint2>();
 	g.rec = a.rec;
 	g.n_rec = a.n_rec;
 	g.dsize = a.dsize;
 	g.status = a.status;
-	HIPCHK(P->ctx, launch_greedy(g, P->greedy_heads, st, ev_built));
+	HIPCHK(P->ctx, launch_greedy(g, P->g.greedy_heads, st, ev_built));
 	return DG_OK;
 }
 
@@ -1186,18 +669,18 @@ static int enqueue_correcting(dg_encode_plan_t* P, EncodeArgs a, hipEvent_t ev_b
 	a.stats = P->stats;
 	a.ctab = P->d_ctab.as<uint32_t>();
 	a.kcls = P->d_kcls.as<uint64_t>();
-	a.max_seeds = (uint32_t)P->max_seeds;
+	a.max_seeds = (uint32_t)P->g.max_seeds;
 	// the LDS build writes every slot of every index; the global
 	// build only fills, so its tables start empty (~0)
 	a.gpairs = P->d_gpairs.as<uint32_t>();
-	a.n_gpairs = P->n_gpairs;
+	a.n_gpairs = (uint32_t)P->g.gpairs.size();
 	HIPCHK(ctx, launch_correcting_clear(a, st));
-	if (P->crc_fused) {
+	if (P->g.crc_fused) {
 		a.crc_out = P->d_crc.as<uint64_t>();
 		a.crc_tab = ctx->d_crc_tables;
 		a.crc_k32 = ctx->d_k32;
 	}
-	HIPCHK(ctx, launch_correcting(a, a.p, st, P->corr_lds_cap, P->qmin, ev_built, ev_fork));
+	HIPCHK(ctx, launch_correcting(a, a.p, st, P->g.corr_lds_cap, P->g.qmin, ev_built, ev_fork));
 	return DG_OK;
 }
 
@@ -1226,12 +709,11 @@ int dg_encode_plan_run(dg_encode_plan_t* P, const uint8_t* d_ref, const uint8_t*
 	// before the differencing.)
 	const bool serial = P->serial_crc;
 	hipStream_t cs = serial ? st : P->side;
-	const bool timed = P->timing && P->calls++ % P->every == 0;   // this run records its events
-	if (timed) P->cur = &P->ev[(size_t)kTimingEvents * (P->runs++ % P->slots)];
+	hipEvent_t* const cur = P->ring.next();   // this run's events (nullptr: it records none)
 	// event k: every stage event, or (DG_TIMING_DOMINANT) only the ones
 	// around the dominant kernel(s) (each extra timing event costs the run
 	// stream a few microseconds); nullptr = not recorded
-	auto ev = [&](int k) -> hipEvent_t { return timed && (timing_mask(P) & (1u << k)) ? P->cur[k] : nullptr; };
+	auto ev = [&](int k) -> hipEvent_t { return cur && (timing_mask(P) & (1u << k)) ? cur[k] : nullptr; };
 	auto rec = [&](int k, hipStream_t s) -> hipError_t {
 		hipEvent_t e = ev(k);
 		return e ? hipEventRecord(e, s) : hipSuccess;
@@ -1243,8 +725,8 @@ int dg_encode_plan_run(dg_encode_plan_t* P, const uint8_t* d_ref, const uint8_t*
 	// transposition pairs, c3s / c4o) runs as a plain plan, the member kernel
 	// and its serialiser skipped, except every kProbeEvery-th run, which
 	// refreshes the count.
-	bool mem = P->members;
-	if (mem && P->route_min && P->route_fb.read() >= P->n) {
+	bool mem = P->g.members;
+	if (mem && P->g.route_min && P->route_fb.read() >= P->n) {
 		if (++P->plain_streak < kProbeEvery) mem = false;
 		else P->plain_streak = 0;
 	}
@@ -1261,15 +743,15 @@ int dg_encode_plan_run(dg_encode_plan_t* P, const uint8_t* d_ref, const uint8_t*
 	// SIMDs and the second round's last pairs trail: c3s 39.1 -> 35.7 ms
 	// (profiles/r06_experiments.md).  Batches that route fewer pairs keep the
 	// pass beside the member chain, whose shadow it is at c6.
-	const bool chain_join = mem && !serial && !P->skip_crc && P->route_min && P->route_fb.read() > 16u * ctx->n_cu;
+	const bool chain_join = mem && !serial && !P->skip_crc && P->g.route_min && P->route_fb.read() > 16u * ctx->n_cu;
 
 	CrcArgs c{};
 	c.arena[0] = d_ref;
 	c.arena[1] = d_ver;
 	c.spans = P->d_crc_spans_r.as<CrcSpanDev>();
 	c.segs = P->d_crc_segs.as<CrcSegDev>();
-	c.n_segs = P->n_crc_segs;
-	c.n_spans = P->n_crc_spans;
+	c.n_segs = (uint32_t)P->g.segs.size();
+	c.n_spans = (uint32_t)P->g.spans.size();
 	c.tables = ctx->d_crc_tables;
 	c.seg_crc = P->d_seg_crc.as<uint64_t>();
 	c.out = P->d_crc.as<uint64_t>();
@@ -1287,7 +769,7 @@ int dg_encode_plan_run(dg_encode_plan_t* P, const uint8_t* d_ref, const uint8_t*
 			// with its whole grid; capped at 2 blocks per CU it took 0.97 ms
 			// there instead of 0.71: C4 731 -> 813 GiB/s)
 			const uint32_t rounds = (P->n + 16u * ctx->n_cu - 1) / (16u * ctx->n_cu);
-			const uint32_t cap = serial || P->crc_fused ? 0u : 2u * ctx->n_cu * std::max(rounds, 1u);
+			const uint32_t cap = serial || P->g.crc_fused ? 0u : 2u * ctx->n_cu * std::max(rounds, 1u);
 			// (member plans: the five-bit row pass, 3.25 KiB of LDS: the byte-table
 			// pass's 16 KiB blocks find no room beside the member kernel and trail
 			// it; the member waves run at a higher issue priority, so the pass
@@ -1316,11 +798,11 @@ int dg_encode_plan_run(dg_encode_plan_t* P, const uint8_t* d_ref, const uint8_t*
 		a.dsize = P->d_dsize.as<uint64_t>();
 		a.status = d_status;
 		a.tables = P->d_tables.as<unsigned long long>();
-		a.qmax = P->qmax;
-		a.n_tables = P->n_tables;
+		a.qmax = P->g.qmax;
+		a.n_tables = P->g.n_tables;
 		a.table_locks = P->d_locks.as<uint32_t>();
 		a.table_tags = P->d_tags.as<uint32_t>();
-		if (P->fused) {   // (DG_FUSED=1, A/B: the onepass waves place and serialise their deltas)
+		if (P->g.fused) {   // (DG_FUSED=1, A/B: the onepass waves place and serialise their deltas)
 			a.out = d_out;
 			a.out_cap = out_cap;
 			a.offsets = d_offsets;
@@ -1333,7 +815,7 @@ int dg_encode_plan_run(dg_encode_plan_t* P, const uint8_t* d_ref, const uint8_t*
 		else if (P->algo == DG_ALGO_GREEDY)
 			rc = enqueue_greedy(P, a, ev(7), st);
 		else
-			rc = enqueue_correcting(P, a, ev(7), P->crc_fused && !serial ? P->ev_fork : nullptr, st);
+			rc = enqueue_correcting(P, a, ev(7), P->g.crc_fused && !serial ? P->ev_fork : nullptr, st);
 		if (rc != DG_OK) return rc;
 		if (P->algo == DG_ALGO_ONEPASS) HIPCHK(ctx, rec(7, st));
 		HIPCHK(ctx, rec(3, st));
@@ -1345,7 +827,7 @@ int dg_encode_plan_run(dg_encode_plan_t* P, const uint8_t* d_ref, const uint8_t*
 	if (serial) {
 		if ((rc = run_crc()) != DG_OK) return rc;
 		if ((rc = run_diff()) != DG_OK) return rc;
-	} else if (P->crc_fused) {
+	} else if (P->g.crc_fused) {
 		// the build writes R's CRC; V's CRC forks after the build (ev_fork,
 		// recorded by launch_correcting) and runs beside the V scan
 		if ((rc = run_diff()) != DG_OK) return rc;
@@ -1366,7 +848,7 @@ int dg_encode_plan_run(dg_encode_plan_t* P, const uint8_t* d_ref, const uint8_t*
 		}
 	}
 
-	if (P->fused) {
+	if (P->g.fused) {
 		// (DG_FUSED=1, A/B) the differencing kernel placed and serialised every
 		// delta; only the header CRCs remain, once the CRC stream has joined
 		if (!serial) HIPCHK(ctx, hipStreamWaitEvent(st, P->ev_join, 0));
@@ -1378,7 +860,7 @@ int dg_encode_plan_run(dg_encode_plan_t* P, const uint8_t* d_ref, const uint8_t*
 
 	// ── exclusive scan of the delta sizes -> packed offsets ──
 	HIPCHK(ctx, launch_scan(P->d_dsize.as<uint64_t>(), d_offsets, P->n, st,
-	                        mem && P->route_min ? P->d_route_cnt.as<uint32_t>() : nullptr, P->route_fb.d));
+	                        mem && P->g.route_min ? P->d_route_cnt.as<uint32_t>() : nullptr, P->route_fb.d));
 	HIPCHK(ctx, rec(4, st));
 
 	// ── serialise + join ──
@@ -1387,7 +869,7 @@ int dg_encode_plan_run(dg_encode_plan_t* P, const uint8_t* d_ref, const uint8_t*
 		// header CRCs (the CRC stream may still be running beside the chains),
 		// then the join, the CRC's combine and the header patch
 		const MemSerArgs m = mem_ser_args(P, d_ver, d_out, out_cap, d_offsets, d_status);
-		HIPCHK(ctx, launch_member_serialize(m, P->n_chunks, ctx->n_cu, st));
+		HIPCHK(ctx, launch_member_serialize(m, P->g.n_chunks, ctx->n_cu, st));
 		if (!serial) HIPCHK(ctx, hipStreamWaitEvent(st, P->ev_join, 0));
 		if (late_fin && !P->skip_crc) HIPCHK(ctx, launch_crc_finalize(c, st));
 		HIPCHK(ctx, launch_crc_patch(d_out, d_offsets, P->d_crc.as<uint64_t>(), d_status, P->n, st));
@@ -1420,8 +902,6 @@ void dg_encode_plan_destroy(dg_encode_plan_t* P) {
 	hipSetDevice(P->ctx->device);
 	hipStreamSynchronize(P->ctx->stream);
 	if (P->side) hipStreamSynchronize(P->side);
-	for (auto& e : P->ev)
-		if (e) hipEventDestroy(e);
 	if (P->ev_fork) hipEventDestroy(P->ev_fork);
 	if (P->ev_join) hipEventDestroy(P->ev_join);
 	if (P->side) hipStreamDestroy(P->side);
@@ -1481,10 +961,7 @@ struct dg_decode_plan {
 	// check when the extents of the arenas overlap)
 	uint64_t ref_end = 0, delta_end = 0, out_end = 0;
 	std::vector<std::pair<uint64_t, uint64_t>> iv_ref, iv_delta, iv_out;
-	bool timing = false;
-	std::vector<hipEvent_t> ev;
-	uint32_t slots = 0, runs = 0, ev_sets = 0;   // ring length; event sets allocated
-	uint32_t every = 1, calls = 0;   // events on every `every`-th run (dg_*_plan_set_timing_every)
+	TimingRing ring;   // kDecEvents events per run
 };
 
 namespace {
@@ -1497,17 +974,15 @@ int dg_decode_plan_create(dg_context_t* ctx, const dg_decode_desc_t* descs, uint
                           int ignore_hash, dg_decode_plan_t** out) {
 	if (!ctx || !out || (n && !descs)) return DG_ERR_INVALID_ARG;
 	*out = nullptr;
+	for (uint32_t i = 0; i < n; ++i)
+		if (descs[i].ref_len >= (1ull << 32) || descs[i].out_cap >= (1ull << 32) + (1ull << 31))
+			return set_err(ctx, DG_ERR_TOO_LARGE, "stream %u exceeds the u32 format", i);
 	hipSetDevice(ctx->device);
 	auto* P = new (std::nothrow) dg_decode_plan_t();
 	if (!P) return DG_ERR_NOMEM;
 	P->ctx = ctx;
 	P->n = n;
 	P->ignore_hash = ignore_hash;
-	for (uint32_t i = 0; i < n; ++i)
-		if (descs[i].ref_len >= (1ull << 32) || descs[i].out_cap >= (1ull << 32) + (1ull << 31)) {
-			delete P;
-			return set_err(ctx, DG_ERR_TOO_LARGE, "stream %u exceeds the u32 format", i);
-		}
 	for (uint32_t i = 0; i < n; ++i) {
 		P->ref_end = std::max(P->ref_end, descs[i].ref_off + descs[i].ref_len);
 		P->delta_end = std::max(P->delta_end, descs[i].delta_off + descs[i].delta_len);
@@ -1527,7 +1002,7 @@ int dg_decode_plan_create(dg_context_t* ctx, const dg_decode_desc_t* descs, uint
 	}
 	const size_t nn = std::max<size_t>(n, 1);
 	if (P->d_desc.alloc(sizeof(dg_decode_desc_t) * nn)) {
-		delete P;
+		dg_decode_plan_destroy(P);
 		return set_err(ctx, DG_ERR_NOMEM, "device allocation failed");
 	}
 	hipStream_t st = ctx->stream;
@@ -1545,34 +1020,17 @@ int dg_decode_plan_create(dg_context_t* ctx, const dg_decode_desc_t* descs, uint
 int dg_decode_plan_set_timing(dg_decode_plan_t* P, int slots) {
 	if (!P || slots < 0) return DG_ERR_INVALID_ARG;
 	hipSetDevice(P->ctx->device);
-	if ((uint32_t)slots > P->ev_sets) {
-		for (auto& e : P->ev) hipEventDestroy(e);
-		P->ev.assign((size_t)kDecEvents * slots, nullptr);
-		P->ev_sets = P->slots = 0;
-		for (auto& e : P->ev)
-			// timing only: no system-scope fence when the event is recorded
-			// (a cache writeback + invalidate per event slowed the timed
-			// steps by 15 %: C2 0.335 -> 0.391 ms with two events per step)
-			if (hipEventCreateWithFlags(&e, hipEventDisableSystemFence) != hipSuccess) {
-				e = nullptr;
-				P->timing = false;
-				return set_err(P->ctx, DG_ERR_HIP, "hipEventCreate failed");
-			}
-		P->ev_sets = (uint32_t)slots;
-	}
-	P->slots = (uint32_t)slots;   // the ring: exactly the last `slots` runs
-	P->timing = slots > 0;
-	P->runs = P->calls = 0;
+	if (!P->ring.set((uint32_t)slots, kDecEvents)) return set_err(P->ctx, DG_ERR_HIP, "hipEventCreate failed");
 	return DG_OK;
 }
 
 // one stage, "decode": the kernel parses, applies and checks both CRCs
 int dg_decode_plan_stage_times(dg_decode_plan_t* P, float* ms, const char** names, int n) {
-	if (!P || !P->slots || !P->runs || n < 1) return 0;
-	const uint32_t used = std::min(P->runs, P->slots);
+	const uint32_t used = P ? P->ring.used() : 0;
+	if (!used || n < 1) return 0;
 	double acc = 0;
 	for (uint32_t s = 0; s < used; ++s) {
-		hipEvent_t* e = &P->ev[(size_t)kDecEvents * s];
+		hipEvent_t* e = P->ring.set_at(s);
 		if (hipEventSynchronize(e[1]) != hipSuccess) return 0;
 		float t = 0;
 		hipEventElapsedTime(&t, e[0], e[1]);
@@ -1585,8 +1043,7 @@ int dg_decode_plan_stage_times(dg_decode_plan_t* P, float* ms, const char** name
 
 int dg_decode_plan_set_timing_every(dg_decode_plan_t* P, int every) {
 	if (!P || every < 1) return DG_ERR_INVALID_ARG;
-	P->every = (uint32_t)every;
-	P->calls = 0;
+	P->ring.set_every((uint32_t)every);
 	return DG_OK;
 }
 
@@ -1626,8 +1083,7 @@ int dg_decode_plan_run(dg_decode_plan_t* P, const uint8_t* d_ref, const uint8_t*
 			return set_err(ctx, DG_ERR_INVALID_ARG, "the output bytes overlap the reference or delta bytes");
 	}
 	hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-	hipEvent_t* ev = nullptr;
-	if (P->timing && P->calls++ % P->every == 0) ev = &P->ev[(size_t)kDecEvents * (P->runs++ % P->slots)];
+	hipEvent_t* const ev = P->ring.next();
 	const bool check = !P->ignore_hash;
 	// parse + apply (encoding.c:111-178, apply.c:229-284), then the CRC-64/XZ
 	// of R and of the output, checked against the header in the same kernel
@@ -1654,8 +1110,6 @@ void dg_decode_plan_destroy(dg_decode_plan_t* P) {
 	if (!P) return;
 	hipSetDevice(P->ctx->device);
 	hipStreamSynchronize(P->ctx->stream);
-	for (auto& e : P->ev)
-		if (e) hipEventDestroy(e);
 	delete P;
 }
 

@@ -14,6 +14,7 @@
 
 #include "../../include/delta_gpu.h"
 #include "dg_device.h"
+#include "dg_plan.h"
 
 namespace {
 
@@ -139,7 +140,8 @@ int dg_encode_batch(dg_context_t* ctx, dg_algorithm_t algo, const uint8_t* const
 	if (verbose)
 		for (uint32_t i = 0; i < n; ++i)
 			if (h_st.as<int32_t>()[i] == DG_OK)
-				dg::print_verbose(plan, i, stats.data() + 8ull * i, h_out.as<uint8_t>() + off[i], off[i + 1] - off[i]);
+				dg::print_verbose(algo, *opts, pairs[i], dg::plan_pp(plan)[i], stats.data() + 8ull * i,
+				                  h_out.as<uint8_t>() + off[i], off[i + 1] - off[i]);
 	dg_encode_plan_destroy(plan);
 	int first_bad = DG_OK;
 	for (uint32_t i = 0; i < n; ++i) {

@@ -7,6 +7,9 @@ host_fuzz.cpp and driven over a corpus of reference-minted deltas
 (tests/golden/*.json), oracle-encoded pairs with many CRWI cycles, and every
 truncation plus seeded byte mutations of each (see host_fuzz.cpp).  The
 oracle only makes inputs here.
+
+The third HIP-free file, dg_plan.cpp (plan geometry, CRC tables, the --verbose
+report), runs under the same sanitizers in tests/test_plan_cpu.py.
 """
 from __future__ import annotations
 
