@@ -40,6 +40,7 @@ from ._lib import (  # noqa: F401
     DiffOptions,
     EncodePlan,
     DecodePlan,
+    InplacePlan,
     LIB_PATH,
     LIMIT_ONEPASS_MEMBERS,
     LIMIT_TABLE_POOL_BYTES,
@@ -62,6 +63,7 @@ from ._lib import (  # noqa: F401
     info,
     lib,
     make_inplace,
+    make_inplace_batch,
     output_size,
     place_commands,
     status_string,
@@ -70,9 +72,9 @@ from ._lib import (  # noqa: F401
 
 __all__ = [
     "ALGO_ONEPASS", "ALGO_CORRECTING", "ALGO_GREEDY", "SEED_LEN", "TABLE_SIZE",
-    "MAX_TABLE_SIZE", "BUF_CAP", "Context", "DeltaError", "DiffOptions", "EncodePlan", "DecodePlan",
+    "MAX_TABLE_SIZE", "BUF_CAP", "Context", "DeltaError", "DiffOptions", "EncodePlan", "DecodePlan", "InplacePlan",
     "crc64_xz", "decode", "default_context", "encode", "encode_batch", "encode_pipelined", "info", "lib",
-    "make_inplace", "status_string", "LIB_PATH", "LIMIT_TABLE_POOL_BYTES",
+    "make_inplace", "make_inplace_batch", "status_string", "LIB_PATH", "LIMIT_TABLE_POOL_BYTES",
     "LIMIT_ONEPASS_MEMBERS", "MEMBERS_AUTO", "MEMBERS_ON", "MEMBERS_OFF",
     "CopyCmd", "AddCmd", "PlacedCopy", "PlacedAdd", "diff", "diff_greedy", "diff_onepass", "diff_correcting",
     "diff_placed", "place_commands", "unplace_commands", "output_size", "encode_delta", "decode_delta",

@@ -74,6 +74,11 @@ class DecodeDesc(C.Structure):
                 ("out_off", C.c_uint64), ("out_cap", C.c_uint64)]
 
 
+class InplaceDesc(C.Structure):   # dg_inplace_desc_t
+    _fields_ = [("ref_off", C.c_uint64), ("ref_len", C.c_uint64),
+                ("delta_off", C.c_uint64), ("delta_cap", C.c_uint64)]
+
+
 class InplaceStats(C.Structure):
     _fields_ = [("already_inplace", C.c_int), ("num_copies", C.c_uint64), ("num_adds", C.c_uint64),
                 ("copy_bytes", C.c_uint64), ("add_bytes", C.c_uint64)]
@@ -170,6 +175,15 @@ def _load() -> C.CDLL:
                                          C.c_uint8 * 8, C.POINTER(Buffer)]),
         "dg_commands_free": (None, [C.POINTER(Commands)]),
         "dg_make_inplace": (C.c_int, [u8p, sz, u8p, sz, C.c_int, C.POINTER(Buffer), C.POINTER(InplaceStats)]),
+        "dg_inplace_plan_create": (C.c_int, [vp, C.POINTER(InplaceDesc), u32, C.c_int, C.POINTER(vp)]),
+        "dg_inplace_plan_create_for": (C.c_int, [vp, vp, C.c_int, C.POINTER(vp)]),
+        "dg_inplace_plan_output_bound": (u64, [vp]),
+        "dg_inplace_plan_run": (C.c_int, [vp, vp, vp, vp, vp, vp, u64, vp, vp, vp]),
+        "dg_inplace_plan_set_timing": (C.c_int, [vp, C.c_int]),
+        "dg_inplace_plan_stage_times": (C.c_int, [vp, C.POINTER(C.c_float), C.POINTER(C.c_char_p), C.c_int]),
+        "dg_inplace_plan_destroy": (None, [vp]),
+        "dg_make_inplace_batch": (C.c_int, [vp, C.POINTER(u8p), C.POINTER(sz), C.POINTER(u8p), C.POINTER(sz), u32,
+                                            C.c_int, C.POINTER(Buffer), C.POINTER(i32)]),
         "dg_synth_edit_pairs_device": (C.c_int, [vp, vp, vp, u32, u64, u64, u64, vp]),
         "dg_synth_shift_pairs_device": (C.c_int, [vp, u64, u32, u64, u64, u32, C.POINTER(Pair),
                                                   C.POINTER(u64), C.POINTER(u64), vp, vp, vp]),
@@ -389,6 +403,59 @@ class DecodePlan:
             pass
 
 
+class InplacePlan:
+    """dg_inplace_plan_t: a batch of standard deltas converted to in-place form
+    on the device.  descs: (ref_off, ref_len, delta_off, delta_cap) per delta, or
+    for_plan: an EncodePlan whose packed output the run converts (pass its
+    offsets and status to run)."""
+
+    def __init__(self, ctx: Context, descs: Optional[Sequence[Tuple[int, int, int, int]]] = None,
+                 policy: str = "localmin", for_plan: Optional["EncodePlan"] = None):
+        self.ctx = ctx
+        h = C.c_void_p()
+        if for_plan is not None:
+            ctx.check(lib.dg_inplace_plan_create_for(ctx.handle, for_plan.handle, POLICIES[policy], C.byref(h)),
+                      "dg_inplace_plan_create_for")
+            self.n = for_plan.n
+        else:
+            n = len(descs)
+            arr = (InplaceDesc * max(n, 1))(*[InplaceDesc(*d) for d in descs])
+            ctx.check(lib.dg_inplace_plan_create(ctx.handle, arr, n, POLICIES[policy], C.byref(h)),
+                      "dg_inplace_plan_create")
+            self.n = n
+        self.handle = h
+
+    @property
+    def output_bound(self) -> int:
+        return lib.dg_inplace_plan_output_bound(self.handle)
+
+    def run(self, d_ref: int, d_delta: int, d_out: int, out_cap: int, d_out_offsets: int, d_status: int,
+            d_delta_offsets: int = 0, d_delta_status: int = 0, stream: int = 0):
+        self.ctx.check(lib.dg_inplace_plan_run(self.handle, d_ref, d_delta, d_delta_offsets or None,
+                                               d_delta_status or None, d_out, out_cap, d_out_offsets, d_status,
+                                               stream or None), "dg_inplace_plan_run")
+
+    def set_timing(self, slots: int = 1):
+        self.ctx.check(lib.dg_inplace_plan_set_timing(self.handle, int(slots)), "set_timing")
+
+    def stage_times(self):
+        ms = (C.c_float * 8)()
+        names = (C.c_char_p * 8)()
+        k = lib.dg_inplace_plan_stage_times(self.handle, ms, names, 8)
+        return {names[i].decode(): ms[i] for i in range(k)}
+
+    def close(self):
+        if self.handle:
+            lib.dg_inplace_plan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def encode(R: bytes, V: bytes, algorithm="onepass", p: int = SEED_LEN, q: int = TABLE_SIZE,
            buf_cap: int = BUF_CAP, max_table: int = MAX_TABLE_SIZE, splay: bool = False,
            inplace: bool = False, policy: str = "localmin",
@@ -437,12 +504,13 @@ def encode_pipelined(pairs: Sequence[Tuple[bytes, bytes]], algorithm="onepass", 
                      q: int = TABLE_SIZE, buf_cap: int = BUF_CAP, max_table: int = MAX_TABLE_SIZE,
                      chunk_bytes: int = 0, pinned: bool = False, align: int = 16, out_cap: Optional[int] = None,
                      ctx: Optional[Context] = None, ctxs: Optional[Sequence[Context]] = None,
-                     splay: bool = False) -> List[bytes]:
+                     splay: bool = False, inplace: bool = False, policy: str = "localmin") -> List[bytes]:
     """Many pairs host-to-host through dg_encode_pipelined (chunked, two chunks in
     flight).  The pairs are laid out in host arenas `align` bytes apart, pinned
     (dg_host_alloc) or pageable (bytearray).  ctxs: one context per device,
     through dg_encode_pipelined_multi (byte-balanced pair ranges, one host
-    thread per device, deltas packed in pair order)."""
+    thread per device, deltas packed in pair order).  inplace: every chunk is
+    converted to in-place deltas on the device after its encode (policy)."""
     ctx = ctx or (ctxs[0] if ctxs else default_context())
     n = len(pairs)
     if n == 0:
@@ -452,7 +520,7 @@ def encode_pipelined(pairs: Sequence[Tuple[bytes, bytes]], algorithm="onepass", 
         ro, vo = (rt + align - 1) // align * align, (vt + align - 1) // align * align
         lay.append((ro, len(r), vo, len(v)))
         rt, vt = ro + len(r), vo + len(v)
-    cap = out_cap if out_cap is not None else sum(len(v) for _, v in pairs) + 64 * n + 64
+    cap = out_cap if out_cap is not None else (2 if inplace else 1) * sum(len(v) for _, v in pairs) + 64 * n + 64
     bufs = []
 
     def host(nbytes):
@@ -473,7 +541,7 @@ def encode_pipelined(pairs: Sequence[Tuple[bytes, bytes]], algorithm="onepass", 
         pa = (Pair * n)(*[Pair(*x) for x in lay])
         offs = (C.c_uint64 * (n + 1))()
         st = (C.c_int32 * n)()
-        o = _opts(p, q, buf_cap, max_table, splay=splay)
+        o = _opts(p, q, buf_cap, max_table, splay=splay, inplace=inplace, policy=policy)
         if ctxs:
             hs = (C.c_void_p * len(ctxs))(*[c.handle for c in ctxs])
             ctx.check(lib.dg_encode_pipelined_multi(hs, len(ctxs), _algo(algorithm), hr, hv, pa, n, C.byref(o),
@@ -505,6 +573,34 @@ def make_inplace(R: bytes, delta: bytes, policy: str = "localmin", stats: bool =
     lib.dg_buffer_free(C.byref(out))
     if stats:
         return res, {k: getattr(st, k) for k, _ in InplaceStats._fields_}
+    return res
+
+
+def make_inplace_batch(items: Sequence[Tuple[bytes, bytes]], policy: str = "localmin",
+                       ctx: Optional[Context] = None) -> List[bytes]:
+    """(R, standard delta) pairs -> in-place deltas, converted on the device in
+    one batch (dg_make_inplace_batch); equal to make_inplace item by item."""
+    ctx = ctx or default_context()
+    n = len(items)
+    if n == 0:
+        return []
+    keep = [(bytes(r), bytes(d)) for r, d in items]
+    rp = (C.POINTER(C.c_uint8) * n)(*[_u8(r) for r, _ in keep])
+    dp = (C.POINTER(C.c_uint8) * n)(*[_u8(d) for _, d in keep])
+    rl = (C.c_size_t * n)(*[len(r) for r, _ in keep])
+    dl = (C.c_size_t * n)(*[len(d) for _, d in keep])
+    outs = (Buffer * n)()
+    st = (C.c_int32 * n)()
+    ctx.check(lib.dg_make_inplace_batch(ctx.handle, rp, rl, dp, dl, n, POLICIES[policy], outs, st),
+              "dg_make_inplace_batch")
+    res, bad = [], None
+    for i in range(n):
+        if st[i] and bad is None:
+            bad = i
+        res.append(C.string_at(outs[i].data, outs[i].len) if outs[i].len else b"")
+        lib.dg_buffer_free(C.byref(outs[i]))
+    if bad is not None:
+        raise DeltaError(st[bad], f"delta {bad}")
     return res
 
 

@@ -4,10 +4,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "../../include/delta_gpu.h"
 #include "dg_layout.h"
-
-typedef struct dg_context dg_context_t;
-typedef struct dg_encode_plan dg_encode_plan_t;
 
 namespace dg {
 
@@ -191,6 +189,13 @@ uint64_t ctx_limits_gen(const dg_context_t* ctx);   // changes with every dg_con
 int ctx_device(const dg_context_t* ctx);            // the context's HIP device
 // the plan's per-pair parameters (n_pairs records; for print_verbose, dg_plan.h)
 const PairPlanDev* plan_pp(const dg_encode_plan_t* P);
+// what dg_inplace_plan_create_for reads of an encode plan, and the context's
+// slot for the in-place conversion module (dg_inplace_host.cpp)
+const dg_pair_t* plan_pairs(const dg_encode_plan_t* P);
+dg_context_t* plan_ctx(const dg_encode_plan_t* P);
+void plan_options(const dg_encode_plan_t* P, dg_algorithm_t* algo, dg_diff_options_t* opts);
+void** ctx_inplace(dg_context_t* ctx, void (*release)(void*));
+int ctx_fail(dg_context_t* ctx, int code, const char* msg);   // records dg_last_error, returns code
 
 // launchers (dg_kernels.hip)
 // (member plans: routed_after, when set, is waited for between the member

@@ -42,6 +42,8 @@ struct dg_context {
 	size_t pin_cap = 0;
 	void* io = nullptr;                 // dg_encode_pipelined's slots (dg_host_io.cpp)
 	void (*io_free)(void*) = nullptr;
+	void* inplace = nullptr;            // the in-place conversion module (dg_inplace_host.cpp)
+	void (*inplace_free)(void*) = nullptr;
 };
 
 uint64_t dg::ctx_limits_gen(const dg_context_t* ctx) { return ctx->limits_gen; }
@@ -50,6 +52,16 @@ int dg::ctx_device(const dg_context_t* ctx) { return ctx->device; }
 void** dg::ctx_io(dg_context_t* ctx, void (*release)(void*)) {
 	ctx->io_free = release;
 	return &ctx->io;
+}
+
+void** dg::ctx_inplace(dg_context_t* ctx, void (*release)(void*)) {
+	ctx->inplace_free = release;
+	return &ctx->inplace;
+}
+
+int dg::ctx_fail(dg_context_t* ctx, int code, const char* msg) {
+	if (ctx) ctx->err = msg;
+	return code;
 }
 
 static int set_err(dg_context_t* ctx, int code, const char* fmt, ...) {
@@ -151,6 +163,7 @@ void dg_context_destroy(dg_context_t* ctx) {
 	hipFree(ctx->d_k32);
 	if (ctx->pin) hipHostFree(ctx->pin);
 	if (ctx->io && ctx->io_free) ctx->io_free(ctx->io);
+	if (ctx->inplace && ctx->inplace_free) ctx->inplace_free(ctx->inplace);
 	if (ctx->stream) hipStreamDestroy(ctx->stream);
 	delete ctx;
 }
@@ -294,6 +307,7 @@ struct dg_encode_plan {
 	dg_diff_options_t opts{};
 	uint32_t n = 0;
 	EncodeGeometry g;   // sizes and layout (dg_plan.h); g.members: member mode in use
+	std::vector<dg_pair_t> pairs;   // the batch layout (dg_inplace_plan_create_for)
 	// device buffers
 	DevBuf d_pairs, d_pplan, d_powc, d_rec, d_nrec, d_dsize, d_crc_spans_r, d_crc_segs,
 	    d_seg_crc, d_crc, d_tables, d_locks, d_tags, d_ctab, d_lookback, d_kcls, d_gpairs, d_prio_flag,
@@ -319,6 +333,12 @@ struct dg_encode_plan {
 };
 
 const PairPlanDev* dg::plan_pp(const dg_encode_plan_t* P) { return P->g.pp.data(); }
+const dg_pair_t* dg::plan_pairs(const dg_encode_plan_t* P) { return P->pairs.data(); }
+dg_context_t* dg::plan_ctx(const dg_encode_plan_t* P) { return P->ctx; }
+void dg::plan_options(const dg_encode_plan_t* P, dg_algorithm_t* algo, dg_diff_options_t* opts) {
+	*algo = P->algo;
+	*opts = P->opts;
+}
 
 static const char* kStageNames[] = {"crc64", "diff", "scan", "serialize+join", "total", "members", "corr_build", "corr_scan"};
 static const char* kGreedyStageNames[] = {"greedy_build", "greedy_scan"};   // stages 6, 7 of a greedy plan
@@ -461,6 +481,7 @@ int dg_encode_plan_create(dg_context_t* ctx, dg_algorithm_t algo, const dg_pair_
 	P->algo = algo;
 	if (opts) P->opts = *opts; else dg_diff_options_default(&P->opts);
 	P->n = n;
+	if (n && pairs) P->pairs.assign(pairs, pairs + n);
 	const int rc = plan_fill(P, pairs);
 	if (rc != DG_OK) {
 		dg_encode_plan_destroy(P);

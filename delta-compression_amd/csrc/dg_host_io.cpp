@@ -186,6 +186,14 @@ struct IoSlot {
 	hipStream_t s = nullptr;
 	hipEvent_t ev = nullptr;
 	dg_encode_plan_t* plan = nullptr;
+	// DG_OPT_INPLACE: the chunk's in-place conversion, made from (and kept
+	// with) the encode plan; it reads d_out / d_off / d_st and writes the *_ip
+	// buffers, which the D2H copies then take
+	dg_inplace_plan_t* ip = nullptr;
+	uint64_t ip_bound = 0;
+	Dev d_out_ip, d_off_ip, d_st_ip;
+	uint64_t cap_out_ip = 0, cap_doff_ip = 0, cap_dst_ip = 0;
+	const void* fin_out = nullptr;   // the device bytes the drain copies to the host
 	std::vector<dg_pair_t> key;   // the plan's layout (chunk-relative)
 	dg_algorithm_t key_algo = DG_ALGO_ONEPASS;
 	dg_diff_options_t key_opts{};
@@ -199,6 +207,7 @@ struct IoSlot {
 	uint32_t p0 = 0, p1 = 0;      // its pairs
 	uint64_t bound = 0;
 	~IoSlot() {
+		if (ip) dg_inplace_plan_destroy(ip);
 		if (plan) dg_encode_plan_destroy(plan);
 		if (ev) hipEventDestroy(ev);
 		if (s) hipStreamDestroy(s);
@@ -330,6 +339,7 @@ int dg_encode_pipelined_multi(dg_context_t* const* ctxs, uint32_t n_ctx, dg_algo
 		for (uint32_t i = r.lo; i < r.hi; ++i) {
 			const uint64_t vl = pairs[i].v_len;
 			bound += algo == DG_ALGO_CORRECTING ? 57 + vl + 22 * (vl / p) : 35 + vl + (vl / p) * (p < 22 ? 22 - p : 0);
+			if ((o.flags >> DG_OPT_INPLACE) & 1) bound += vl;   // COPYs turned into ADD payload
 		}
 		try {
 			r.out.resize(std::max<uint64_t>(bound, 1));
@@ -422,7 +432,6 @@ int dg_encode_pipelined(dg_context_t* ctx, dg_algorithm_t algo, const uint8_t* h
 	if (!ctx || !out_offsets || (n && (!pairs || !h_ref || !h_ver || !h_out))) return DG_ERR_INVALID_ARG;
 	out_offsets[0] = 0;
 	if (n == 0) return DG_OK;
-	if (opts && ((opts->flags >> DG_OPT_INPLACE) & 1)) return DG_ERR_UNSUPPORTED;   // host step: dg_encode_batch
 	// the calling thread's current device becomes the context's before any
 	// stream or event of it is made (a new host thread starts on device 0),
 	// and is the caller's again on return
@@ -431,6 +440,12 @@ int dg_encode_pipelined(dg_context_t* ctx, dg_algorithm_t algo, const uint8_t* h
 	dg_diff_options_t o;
 	if (opts) o = *opts; else dg_diff_options_default(&o);
 	if (chunk_bytes == 0) chunk_bytes = 256ull << 20;
+	// DG_OPT_INPLACE: the standard encode, then the device conversion on the
+	// same stream (main.c:279-292 with --inplace)
+	const bool inplace = (o.flags >> DG_OPT_INPLACE) & 1;
+	const int policy = ((o.flags >> DG_OPT_POLICY_CONSTANT) & 1) ? DG_POLICY_CONSTANT : DG_POLICY_LOCALMIN;
+	dg_diff_options_t o_enc = o;
+	o_enc.flags &= ~((1ull << DG_OPT_INPLACE) | (1ull << DG_OPT_POLICY_CONSTANT));
 	void** io = dg::ctx_io(ctx, io_release);
 	if (!*io) *io = new (std::nothrow) IoState();
 	if (!*io) return DG_ERR_NOMEM;
@@ -484,11 +499,11 @@ int dg_encode_pipelined(dg_context_t* ctx, dg_algorithm_t algo, const uint8_t* h
 		}
 		if (total) {
 			if (out_pinned) {
-				if (hipMemcpyAsync(h_out + out_pos, sl.d_out.p, total, hipMemcpyDeviceToHost, sl.s) != hipSuccess)
+				if (hipMemcpyAsync(h_out + out_pos, sl.fin_out, total, hipMemcpyDeviceToHost, sl.s) != hipSuccess)
 					return DG_ERR_HIP;
 			} else {
 				if (!grow(sl.h_out, sl.cap_hout, total)) return DG_ERR_NOMEM;
-				if (hipMemcpyAsync(sl.h_out.p, sl.d_out.p, total, hipMemcpyDeviceToHost, sl.s) != hipSuccess ||
+				if (hipMemcpyAsync(sl.h_out.p, sl.fin_out, total, hipMemcpyDeviceToHost, sl.s) != hipSuccess ||
 				    hipStreamSynchronize(sl.s) != hipSuccess)
 					return DG_ERR_HIP;
 				par_memcpy(h_out + out_pos, sl.h_out.p, total);
@@ -545,9 +560,19 @@ int dg_encode_pipelined(dg_context_t* ctx, dg_algorithm_t algo, const uint8_t* h
 		                  sl.key_limits == lim && sl.key.size() == rel.size() &&
 		                  !memcmp(sl.key.data(), rel.data(), m * sizeof(dg_pair_t));
 		if (!same) {
+			if (sl.ip) dg_inplace_plan_destroy(sl.ip);
+			sl.ip = nullptr;
 			if (sl.plan) dg_encode_plan_destroy(sl.plan);
 			sl.plan = nullptr;
-			if ((rc = dg_encode_plan_create(ctx, algo, rel.data(), m, &o, &sl.plan)) != DG_OK) break;
+			if ((rc = dg_encode_plan_create(ctx, algo, rel.data(), m, &o_enc, &sl.plan)) != DG_OK) break;
+			if (inplace) {
+				if ((rc = dg_inplace_plan_create_for(ctx, sl.plan, policy, &sl.ip)) != DG_OK) {
+					dg_encode_plan_destroy(sl.plan);   // never a cached plan without its conversion
+					sl.plan = nullptr;
+					break;
+				}
+				sl.ip_bound = dg_inplace_plan_output_bound(sl.ip);
+			}
 			sl.key = rel;
 			sl.key_algo = algo;
 			sl.key_opts = o;
@@ -557,7 +582,9 @@ int dg_encode_pipelined(dg_context_t* ctx, dg_algorithm_t algo, const uint8_t* h
 		if (!grow(sl.d_ref, sl.cap_ref, rn) || !grow(sl.d_ver, sl.cap_ver, vn) ||
 		    !grow(sl.d_out, sl.cap_out, sl.bound) || !grow(sl.d_off, sl.cap_doff, 8ull * (m + 1)) ||
 		    !grow(sl.d_st, sl.cap_dst, 4ull * m) || !grow(sl.h_off, sl.cap_hoff, 8ull * (m + 1)) ||
-		    !grow(sl.h_st, sl.cap_hst, 4ull * m)) {
+		    !grow(sl.h_st, sl.cap_hst, 4ull * m) ||
+		    (inplace && (!grow(sl.d_out_ip, sl.cap_out_ip, sl.ip_bound) || !grow(sl.d_off_ip, sl.cap_doff_ip, 8ull * (m + 1)) ||
+		                 !grow(sl.d_st_ip, sl.cap_dst_ip, 4ull * m)))) {
 			rc = DG_ERR_NOMEM;
 			break;
 		}
@@ -577,8 +604,20 @@ int dg_encode_pipelined(dg_context_t* ctx, dg_algorithm_t algo, const uint8_t* h
 		if ((rc = dg_encode_plan_run(sl.plan, sl.d_ref.as<uint8_t>(), sl.d_ver.as<uint8_t>(), sl.d_out.as<uint8_t>(),
 		                             sl.bound, sl.d_off.as<uint64_t>(), sl.d_st.as<int32_t>(), sl.s)) != DG_OK)
 			break;
-		if (hipMemcpyAsync(sl.h_off.p, sl.d_off.p, 8ull * (m + 1), hipMemcpyDeviceToHost, sl.s) != hipSuccess ||
-		    hipMemcpyAsync(sl.h_st.p, sl.d_st.p, 4ull * m, hipMemcpyDeviceToHost, sl.s) != hipSuccess ||
+		const void* fin_off = sl.d_off.p;
+		const void* fin_st = sl.d_st.p;
+		sl.fin_out = sl.d_out.p;
+		if (inplace) {
+			if ((rc = dg_inplace_plan_run(sl.ip, sl.d_ref.as<uint8_t>(), sl.d_out.as<uint8_t>(), sl.d_off.as<uint64_t>(),
+			                              sl.d_st.as<int32_t>(), sl.d_out_ip.as<uint8_t>(), sl.ip_bound,
+			                              sl.d_off_ip.as<uint64_t>(), sl.d_st_ip.as<int32_t>(), sl.s)) != DG_OK)
+				break;
+			fin_off = sl.d_off_ip.p;
+			fin_st = sl.d_st_ip.p;
+			sl.fin_out = sl.d_out_ip.p;
+		}
+		if (hipMemcpyAsync(sl.h_off.p, fin_off, 8ull * (m + 1), hipMemcpyDeviceToHost, sl.s) != hipSuccess ||
+		    hipMemcpyAsync(sl.h_st.p, fin_st, 4ull * m, hipMemcpyDeviceToHost, sl.s) != hipSuccess ||
 		    hipEventRecord(sl.ev, sl.s) != hipSuccess) {
 			rc = DG_ERR_HIP;
 			break;

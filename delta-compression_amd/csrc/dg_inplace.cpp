@@ -1,10 +1,12 @@
-// dg_inplace.cpp — in-place delta conversion on the host
+// dg_inplace.cpp — in-place delta conversion of one delta on the host
 // (src/c/inplace.c:272-736, Burns, Long & Stockmeyer, IEEE TKDE 2003).
 //
-// A graph algorithm over a few thousand COPY commands per delta, so it stays
-// on the CPU; it consumes the GPU encoder's output
-// (or any standard delta) and emits a delta whose commands can be applied in
-// order inside one buffer holding R.
+// It consumes the GPU encoder's output (or any standard delta) and emits a
+// delta whose commands can be applied in order inside one buffer holding R.
+// Batches are converted on the device by dg_inplace_dev.hip, which this
+// function is the comparator of and the fallback for deltas whose commands
+// are not placed sequentially; it keeps explicit adjacency lists, the device
+// the interval-range form of dg_inplace_core.h.
 //
 // The result must be byte-identical to the reference's, so every ordering
 // the reference exposes is reproduced:

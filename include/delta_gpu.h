@@ -71,7 +71,8 @@ extern "C" {
 typedef enum {
 	DG_OK              = 0,
 	DG_ERR_INVALID_ARG = 1,
-	DG_ERR_UNSUPPORTED = 2,   /* --splay with onepass or correcting, --inplace on a plan */
+	DG_ERR_UNSUPPORTED = 2,   /* --splay with onepass or correcting, --inplace on an
+	                             encode plan, a delta the device converter leaves to the host */
 	DG_ERR_TOO_LARGE   = 3,   /* a buffer >= 4 GiB */
 	DG_ERR_NO_DEVICE   = 4,
 	DG_ERR_HIP         = 5,
@@ -282,7 +283,10 @@ int dg_encode_batch(dg_context_t *ctx, dg_algorithm_t algo,
  * places every pair's streams at 16-byte offsets on the device (so unaligned
  * pageable layouts still take the LDS-window kernels).  Device buffers and
  * plans are kept too: a chunk with the same layout, options and context
- * limits as the slot's last one reuses its plan.
+ * limits as the slot's last one reuses its plan.  With DG_OPT_INPLACE in
+ * opts->flags every chunk's encode is followed on the same stream by its
+ * in-place conversion (dg_inplace_plan_*, policy from DG_OPT_POLICY_CONSTANT)
+ * and the converted deltas are what lands in h_out.
  * Returns DG_OK (per-pair failures in status), DG_ERR_CAPACITY when h_out is
  * too small (the pairs that did not fit get status DG_ERR_CAPACITY and
  * out_offsets equal to the bytes written so far), or the first failure when
@@ -455,16 +459,17 @@ int dg_encode_commands(const dg_placed_command_t *cmds, size_t n, int inplace,
                        uint64_t version_size, const uint8_t src_crc[DG_CRC_SIZE],
                        const uint8_t dst_crc[DG_CRC_SIZE], dg_buffer_t *out);
 
-/* ── in-place conversion (host; src/c/inplace.c:272-736) ───────────────────
+/* ── in-place conversion (src/c/inplace.c:272-736), one delta on the host ──
  *
  * Converts a standard delta against R into an in-place delta: the chain of
  * main.c `inplace` (main.c:427-480) = delta_decode -> delta_unplace_commands
  * -> delta_make_inplace(policy) -> delta_encode(inplace = true), byte for
  * byte.  A delta that is already in-place is returned unchanged
- * (stats->already_inplace = 1).  Pure host code: no context, no GPU.  The
- * encoders produce in-place deltas by running this on their output
- * (dg_encode / dg_encode_batch with DG_OPT_INPLACE, policy from
- * dg_diff_options_t.flags bit DG_OPT_POLICY_CONSTANT). */
+ * (stats->already_inplace = 1).  Pure host code: no context, no GPU.
+ * dg_encode / dg_encode_batch with DG_OPT_INPLACE (policy from
+ * dg_diff_options_t.flags bit DG_OPT_POLICY_CONSTANT) run this on their
+ * output; dg_encode_pipelined with DG_OPT_INPLACE and dg_make_inplace_batch
+ * convert on the device instead (dg_inplace_plan_*, below). */
 #define DG_POLICY_LOCALMIN 0
 #define DG_POLICY_CONSTANT 1
 typedef struct {
@@ -476,6 +481,80 @@ typedef struct {
 int dg_make_inplace(const uint8_t *r, size_t r_len, const uint8_t *delta,
                     size_t delta_len, int policy, dg_buffer_t *out,
                     dg_inplace_stats_t *stats);
+
+/* ── in-place conversion of a batch on the device ──────────────────────────
+ *
+ * The same conversion, byte for byte, for N standard deltas in one device
+ * arena against N references in another: one wave per delta orders the
+ * copies (the CRWI digraph in interval-range form), the size scan
+ * packs the outputs, one block per delta writes them.  A run is two kernels
+ * and the scan on one stream: no allocation, no host synchronisation.
+ *
+ * The device converts deltas whose commands are placed sequentially (each
+ * dst = the sum of the earlier lengths), which every encoder here and
+ * delta_place_commands emit; any other stream gets DG_ERR_UNSUPPORTED (the
+ * host function sorts such commands first).  Per-stream status: DG_OK,
+ * DG_ERR_MALFORMED (bad magic, a field or payload past the stream's end, an
+ * unknown command, a COPY reading past |R|), DG_ERR_UNSUPPORTED, or
+ * DG_ERR_CAPACITY (the stream is longer than delta_cap or holds more commands
+ * than its capacity allows, or its output ends past out_cap); a nonzero
+ * incoming d_delta_status[i] is passed on.  A failed stream's output is
+ * empty (for DG_ERR_CAPACITY from out_cap the offsets still count its size,
+ * as dg_encode_plan_run's do) and its neighbours are untouched.  A delta that
+ * is already in-place is copied through.
+ *
+ * Output: packed like the encode plan's, delta i at
+ * d_out[d_out_offsets[i] .. d_out_offsets[i+1]), n + 1 offsets.  With
+ * d_delta_offsets (n + 1 entries, as dg_encode_plan_run writes them) stream i
+ * is d_delta[d_delta_offsets[i] .. d_delta_offsets[i+1]) and delta_cap only
+ * bounds its length; with NULL it is exactly delta_cap bytes at delta_off.
+ * So dg_encode_plan_run -> dg_inplace_plan_run chain on one stream with no
+ * host step between them.
+ *
+ * Work memory is allocated at plan creation from each delta's capacity, about
+ * 73 bytes per possible COPY ((delta_cap - 25) / 13 of them; a plan made from
+ * an encode plan uses the encoder's record capacity) and 8 per possible ADD;
+ * DG_ERR_NOMEM when it cannot be had.  Like the greedy encoder, a
+ * pathological delta (neighbour ranges totalling O(n^2)) holds its wave for
+ * as long as it takes while the rest of the batch proceeds.
+ *
+ * The kernels live in dg_inplace.hsaco beside libdeltagpu.so and are loaded
+ * on first use; DG_ERR_HIP with the path in dg_last_error when it is missing.
+ * Stage timing as for the encode plan: "order", "scan", "emit", "total". */
+typedef struct {
+	uint64_t ref_off, ref_len;       /* R_i in the reference arena */
+	uint64_t delta_off, delta_cap;   /* standard delta i: start, and most bytes it may have */
+} dg_inplace_desc_t;
+typedef struct dg_inplace_plan dg_inplace_plan_t;
+
+int dg_inplace_plan_create(dg_context_t *ctx, const dg_inplace_desc_t *descs /* host */,
+                           uint32_t n, int policy, dg_inplace_plan_t **out);
+/* Geometry from an encode plan: pair i's R span, its worst-case delta size
+ * and its copy count (the record capacity). */
+int dg_inplace_plan_create_for(dg_context_t *ctx, const dg_encode_plan_t *enc,
+                               int policy, dg_inplace_plan_t **out);
+/* Upper bound of the packed output: per delta its capacity plus the version
+ * bytes its COPYs can turn into ADD payload (for a plan made from
+ * descriptors, max copies x |R| capped at 4 GiB: pass a smaller out_cap when
+ * the version sizes are known). */
+uint64_t dg_inplace_plan_output_bound(const dg_inplace_plan_t *plan);
+int dg_inplace_plan_run(dg_inplace_plan_t *plan, const uint8_t *d_ref,
+                        const uint8_t *d_delta, const uint64_t *d_delta_offsets,
+                        const int32_t *d_delta_status, uint8_t *d_out,
+                        uint64_t out_cap, uint64_t *d_out_offsets,
+                        int32_t *d_status, void *stream);
+int dg_inplace_plan_set_timing(dg_inplace_plan_t *plan, int slots);
+int dg_inplace_plan_stage_times(dg_inplace_plan_t *plan, float *ms,
+                                const char **names, int n);
+void dg_inplace_plan_destroy(dg_inplace_plan_t *plan);
+
+/* Host buffers in, host buffers out (outs[i] malloc'd, status[i] may be
+ * NULL): the batch converted on the device; a stream the device reports
+ * DG_ERR_UNSUPPORTED is converted by dg_make_inplace.  Returns DG_OK (per-
+ * stream failures in status) or the first failure when status is NULL. */
+int dg_make_inplace_batch(dg_context_t *ctx, const uint8_t *const *r, const size_t *r_len,
+                          const uint8_t *const *delta, const size_t *delta_len,
+                          uint32_t n, int policy, dg_buffer_t *outs, int32_t *status);
 
 /* ── synthetic batch generators (bench / test inputs, on the device) ─────
  * Workload definitions in DESIGN.md ("Synthetic inputs"); the oracle's
