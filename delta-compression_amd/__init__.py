@@ -11,6 +11,8 @@ Names and argument meanings follow the reference's interface for this path:
 * ``EncodePlan``                    — device-resident batches (the hot path).
 * ``crc64_xz(data)``                — ``delta_crc64_xz`` (src/c/delta.h:294).
 * ``decode(R, delta)``              — ``delta decode`` (main.c:323-400).
+* ``UpdatePlan`` / ``update_batch`` — an in-place delta applied in the buffer
+  that holds R (apply.c:253-284), validated whole before the first store.
 * ``info(delta)``                   — ``delta info`` (main.c:402-425).
 * ``diff`` / ``diff_greedy`` / ``diff_onepass`` / ``diff_correcting``, ``place_commands``,
   ``unplace_commands``, ``encode_delta``, ``decode_delta`` — the command-list
@@ -41,6 +43,7 @@ from ._lib import (  # noqa: F401
     EncodePlan,
     DecodePlan,
     InplacePlan,
+    UpdatePlan,
     LIB_PATH,
     LIMIT_ONEPASS_MEMBERS,
     LIMIT_TABLE_POOL_BYTES,
@@ -64,6 +67,7 @@ from ._lib import (  # noqa: F401
     lib,
     make_inplace,
     make_inplace_batch,
+    update_batch,
     output_size,
     place_commands,
     status_string,
@@ -72,9 +76,9 @@ from ._lib import (  # noqa: F401
 
 __all__ = [
     "ALGO_ONEPASS", "ALGO_CORRECTING", "ALGO_GREEDY", "SEED_LEN", "TABLE_SIZE",
-    "MAX_TABLE_SIZE", "BUF_CAP", "Context", "DeltaError", "DiffOptions", "EncodePlan", "DecodePlan", "InplacePlan",
+    "MAX_TABLE_SIZE", "BUF_CAP", "Context", "DeltaError", "DiffOptions", "EncodePlan", "DecodePlan", "InplacePlan", "UpdatePlan",
     "crc64_xz", "decode", "default_context", "encode", "encode_batch", "encode_pipelined", "info", "lib",
-    "make_inplace", "make_inplace_batch", "status_string", "LIB_PATH", "LIMIT_TABLE_POOL_BYTES",
+    "make_inplace", "make_inplace_batch", "update_batch", "status_string", "LIB_PATH", "LIMIT_TABLE_POOL_BYTES",
     "LIMIT_ONEPASS_MEMBERS", "MEMBERS_AUTO", "MEMBERS_ON", "MEMBERS_OFF",
     "CopyCmd", "AddCmd", "PlacedCopy", "PlacedAdd", "diff", "diff_greedy", "diff_onepass", "diff_correcting",
     "diff_placed", "place_commands", "unplace_commands", "output_size", "encode_delta", "decode_delta",

@@ -79,6 +79,11 @@ class InplaceDesc(C.Structure):   # dg_inplace_desc_t
                 ("delta_off", C.c_uint64), ("delta_cap", C.c_uint64)]
 
 
+class UpdateDesc(C.Structure):   # dg_update_desc_t
+    _fields_ = [("buf_off", C.c_uint64), ("buf_cap", C.c_uint64), ("ref_len", C.c_uint64),
+                ("delta_off", C.c_uint64), ("delta_len", C.c_uint64)]
+
+
 class InplaceStats(C.Structure):
     _fields_ = [("already_inplace", C.c_int), ("num_copies", C.c_uint64), ("num_adds", C.c_uint64),
                 ("copy_bytes", C.c_uint64), ("add_bytes", C.c_uint64)]
@@ -184,6 +189,13 @@ def _load() -> C.CDLL:
         "dg_inplace_plan_destroy": (None, [vp]),
         "dg_make_inplace_batch": (C.c_int, [vp, C.POINTER(u8p), C.POINTER(sz), C.POINTER(u8p), C.POINTER(sz), u32,
                                             C.c_int, C.POINTER(Buffer), C.POINTER(i32)]),
+        "dg_update_plan_create": (C.c_int, [vp, C.POINTER(UpdateDesc), u32, C.c_int, C.POINTER(vp)]),
+        "dg_update_plan_run": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
+        "dg_update_plan_set_timing": (C.c_int, [vp, C.c_int]),
+        "dg_update_plan_stage_times": (C.c_int, [vp, C.POINTER(C.c_float), C.POINTER(C.c_char_p), C.c_int]),
+        "dg_update_plan_destroy": (None, [vp]),
+        "dg_update_batch": (C.c_int, [vp, C.POINTER(u8p), C.POINTER(sz), C.POINTER(sz), C.POINTER(u8p), C.POINTER(sz),
+                                      u32, C.c_int, C.POINTER(sz), C.POINTER(i32)]),
         "dg_synth_edit_pairs_device": (C.c_int, [vp, vp, vp, u32, u64, u64, u64, vp]),
         "dg_synth_shift_pairs_device": (C.c_int, [vp, u64, u32, u64, u64, u32, C.POINTER(Pair),
                                                   C.POINTER(u64), C.POINTER(u64), vp, vp, vp]),
@@ -456,6 +468,49 @@ class InplacePlan:
             pass
 
 
+class UpdatePlan:
+    """dg_update_plan_t: a batch of in-place deltas applied in place on the
+    device: each stream's buffer, which holds R, becomes V.  descs: (buf_off,
+    buf_cap, ref_len, delta_off, delta_len) per stream.  A stream that fails
+    validation (status other than 0 and 10) keeps every byte."""
+
+    def __init__(self, ctx: Context, descs: Sequence[Tuple[int, int, int, int, int]], ignore_hash: bool = False):
+        self.ctx = ctx
+        n = len(descs)
+        arr = (UpdateDesc * max(n, 1))(*[UpdateDesc(*d) for d in descs])
+        h = C.c_void_p()
+        ctx.check(lib.dg_update_plan_create(ctx.handle, arr, n, int(ignore_hash), C.byref(h)),
+                  "dg_update_plan_create")
+        self.handle = h
+        self.n = n
+
+    def run(self, d_buf: int, d_delta: int, d_out_len: int, d_status: int, d_delta_offsets: int = 0,
+            d_delta_status: int = 0, stream: int = 0):
+        self.ctx.check(lib.dg_update_plan_run(self.handle, d_buf, d_delta, d_delta_offsets or None,
+                                              d_delta_status or None, d_out_len, d_status, stream or None),
+                       "dg_update_plan_run")
+
+    def set_timing(self, slots: int = 1):
+        self.ctx.check(lib.dg_update_plan_set_timing(self.handle, int(slots)), "set_timing")
+
+    def stage_times(self):
+        ms = (C.c_float * 8)()
+        names = (C.c_char_p * 8)()
+        k = lib.dg_update_plan_stage_times(self.handle, ms, names, 8)
+        return {names[i].decode(): ms[i] for i in range(k)}
+
+    def close(self):
+        if self.handle:
+            lib.dg_update_plan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def encode(R: bytes, V: bytes, algorithm="onepass", p: int = SEED_LEN, q: int = TABLE_SIZE,
            buf_cap: int = BUF_CAP, max_table: int = MAX_TABLE_SIZE, splay: bool = False,
            inplace: bool = False, policy: str = "localmin",
@@ -601,6 +656,42 @@ def make_inplace_batch(items: Sequence[Tuple[bytes, bytes]], policy: str = "loca
         lib.dg_buffer_free(C.byref(outs[i]))
     if bad is not None:
         raise DeltaError(st[bad], f"delta {bad}")
+    return res
+
+
+def update_batch(items: Sequence[Tuple[bytes, bytes]], ignore_hash: bool = False,
+                 ctx: Optional[Context] = None, status: bool = False):
+    """(R, in-place delta) pairs -> V, each applied on the device in a buffer of
+    max(|R|, version size) bytes that holds R (dg_update_batch).  Raises
+    DeltaError for the first failing item, as make_inplace_batch does; with
+    status=True returns (results, statuses) instead, a result being None where
+    the item's buffer was left as it was (every status but 0 and 10)."""
+    ctx = ctx or default_context()
+    n = len(items)
+    if n == 0:
+        return ([], []) if status else []
+    keep = [(bytes(r), bytes(d)) for r, d in items]
+    caps = []
+    for r, d in keep:
+        vs = int.from_bytes(d[5:9], "big") if len(d) >= 25 else 0
+        caps.append(max(len(r), vs, 1))
+    bufs = [(C.c_uint8 * cap)() for cap in caps]
+    for b, (r, _) in zip(bufs, keep):
+        C.memmove(b, r, len(r))
+    bp = (C.POINTER(C.c_uint8) * n)(*[C.cast(b, C.POINTER(C.c_uint8)) for b in bufs])
+    dp = (C.POINTER(C.c_uint8) * n)(*[_u8(d) for _, d in keep])
+    rl = (C.c_size_t * n)(*[len(r) for r, _ in keep])
+    bc = (C.c_size_t * n)(*caps)
+    dl = (C.c_size_t * n)(*[len(d) for _, d in keep])
+    ol = (C.c_size_t * n)()
+    st = (C.c_int32 * n)()
+    ctx.check(lib.dg_update_batch(ctx.handle, bp, rl, bc, dp, dl, n, int(ignore_hash), ol, st), "dg_update_batch")
+    res = [bytes(bufs[i][:ol[i]]) if st[i] in (0, 10) else None for i in range(n)]
+    if status:
+        return res, list(st)
+    for i in range(n):
+        if st[i]:
+            raise DeltaError(st[i], f"delta {i}")
     return res
 
 

@@ -42,8 +42,10 @@ struct dg_context {
 	size_t pin_cap = 0;
 	void* io = nullptr;                 // dg_encode_pipelined's slots (dg_host_io.cpp)
 	void (*io_free)(void*) = nullptr;
-	void* inplace = nullptr;            // the in-place conversion module (dg_inplace_host.cpp)
-	void (*inplace_free)(void*) = nullptr;
+	// code objects loaded at run time: the in-place conversion module
+	// (dg_inplace_host.cpp), the in-place update module (dg_update_host.cpp)
+	void* module[kCtxModules] = {};
+	void (*module_free[kCtxModules])(void*) = {};
 };
 
 uint64_t dg::ctx_limits_gen(const dg_context_t* ctx) { return ctx->limits_gen; }
@@ -54,10 +56,14 @@ void** dg::ctx_io(dg_context_t* ctx, void (*release)(void*)) {
 	return &ctx->io;
 }
 
-void** dg::ctx_inplace(dg_context_t* ctx, void (*release)(void*)) {
-	ctx->inplace_free = release;
-	return &ctx->inplace;
+void** dg::ctx_module(dg_context_t* ctx, int slot, void (*release)(void*)) {
+	ctx->module_free[slot] = release;
+	return &ctx->module[slot];
 }
+
+void** dg::ctx_inplace(dg_context_t* ctx, void (*release)(void*)) { return ctx_module(ctx, kCtxModInplace, release); }
+
+const uint64_t* dg::ctx_crc_tables(const dg_context_t* ctx) { return ctx->d_crc_tables; }
 
 int dg::ctx_fail(dg_context_t* ctx, int code, const char* msg) {
 	if (ctx) ctx->err = msg;
@@ -163,7 +169,8 @@ void dg_context_destroy(dg_context_t* ctx) {
 	hipFree(ctx->d_k32);
 	if (ctx->pin) hipHostFree(ctx->pin);
 	if (ctx->io && ctx->io_free) ctx->io_free(ctx->io);
-	if (ctx->inplace && ctx->inplace_free) ctx->inplace_free(ctx->inplace);
+	for (int k = 0; k < kCtxModules; ++k)
+		if (ctx->module[k] && ctx->module_free[k]) ctx->module_free[k](ctx->module[k]);
 	if (ctx->stream) hipStreamDestroy(ctx->stream);
 	delete ctx;
 }

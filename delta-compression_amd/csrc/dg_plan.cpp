@@ -553,4 +553,35 @@ void print_verbose(dg_algorithm_t algo, const dg_diff_options_t& o, const dg_pai
 	print_command_stats(cmds);
 }
 
+// ── update plan: descriptor checks ──
+
+int update_check_descs(const dg_update_desc_t* descs, uint32_t n, std::string& err) {
+	char msg[160];
+	std::vector<std::pair<uint64_t, uint64_t>> iv;   // the non-empty buffer regions
+	iv.reserve(n);
+	for (uint32_t i = 0; i < n; ++i) {
+		const dg_update_desc_t& d = descs[i];
+		if (d.buf_cap >= (1ull << 32) || d.ref_len >= (1ull << 32) || d.delta_len >= (1ull << 32)) {
+			snprintf(msg, sizeof msg, "update plan: stream %u: a buffer or a length of 4 GiB or more does not fit the u32 format", i);
+			err = msg;
+			return DG_ERR_TOO_LARGE;
+		}
+		if (d.buf_off + d.buf_cap < d.buf_off || d.delta_off + d.delta_len < d.delta_off) {
+			snprintf(msg, sizeof msg, "update plan: stream %u: a region wraps the address space", i);
+			err = msg;
+			return DG_ERR_INVALID_ARG;
+		}
+		if (d.buf_cap) iv.push_back({d.buf_off, d.buf_off + d.buf_cap});
+	}
+	std::sort(iv.begin(), iv.end());
+	for (size_t k = 1; k < iv.size(); ++k)
+		if (iv[k].first < iv[k - 1].second) {
+			snprintf(msg, sizeof msg, "update plan: the buffer regions at %llu and %llu overlap",
+			         (unsigned long long)iv[k - 1].first, (unsigned long long)iv[k].first);
+			err = msg;
+			return DG_ERR_INVALID_ARG;
+		}
+	return DG_OK;
+}
+
 }  // namespace dg

@@ -88,6 +88,11 @@ struct EncodeGeometry {
 int encode_geometry(dg_algorithm_t algo, const dg_diff_options_t& o, const dg_pair_t* pairs, uint32_t n,
                     const PlanEnv& env, EncodeGeometry& g, std::string& err);
 
+// dg_update_plan_create's descriptor checks: DG_OK, DG_ERR_TOO_LARGE (a buffer
+// or a length of 4 GiB or more) or DG_ERR_INVALID_ARG (a region wrapping the
+// address space, two buffer regions overlapping), with its message in err
+int update_check_descs(const dg_update_desc_t* descs, uint32_t n, std::string& err);
+
 // --verbose: the reference's diagnostic lines for one pair to stderr, from
 // its parameters, its 8 device counters (copied to the host; may be NULL for
 // onepass) and its delta

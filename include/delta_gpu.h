@@ -17,6 +17,10 @@
  *   delta_decode + delta_apply_placed(_inplace)     dg_decode / dg_decode_batch
  *     + CRC checks (encoding.c:111-178,
  *       apply.c:229-284, main.c:341-385)
+ *   delta_apply_placed_inplace in the caller's      dg_update_plan_run / dg_update_batch
+ *     own buffer (apply.c:253-284), after the        (the buffer that holds R becomes V;
+ *     whole parse and the source CRC check           nothing is stored before both passed)
+ *     (encoding.c:111-178, main.c:341-356)
  *   delta_crc64_xz (delta.h:294)                    dg_crc64_xz / dg_crc64_xz_batch_device
  *
  * Output bytes are identical to the reference's `delta encode` at the same
@@ -72,7 +76,8 @@ typedef enum {
 	DG_OK              = 0,
 	DG_ERR_INVALID_ARG = 1,
 	DG_ERR_UNSUPPORTED = 2,   /* --splay with onepass or correcting, --inplace on an
-	                             encode plan, a delta the device converter leaves to the host */
+	                             encode plan, a delta the device converter leaves to the host,
+	                             a standard delta given to dg_update_plan_run */
 	DG_ERR_TOO_LARGE   = 3,   /* a buffer >= 4 GiB */
 	DG_ERR_NO_DEVICE   = 4,
 	DG_ERR_HIP         = 5,
@@ -555,6 +560,87 @@ void dg_inplace_plan_destroy(dg_inplace_plan_t *plan);
 int dg_make_inplace_batch(dg_context_t *ctx, const uint8_t *const *r, const size_t *r_len,
                           const uint8_t *const *delta, const size_t *delta_len,
                           uint32_t n, int policy, dg_buffer_t *outs, int32_t *status);
+
+/* ── in-place update of a batch on the device: R becomes V in its own buffer ──
+ *
+ * The consuming side of in-place deltas (Burns et al.; inplace.c, apply.c:
+ * 253-284): stream i's buffer, buf_cap bytes at buf_off of one device arena,
+ * holds R_i in its first ref_len bytes; after the run it holds V_i in its first
+ * version_size bytes.  No second arena and no copy of R: against
+ * dg_decode_plan_run, which needs the reference arena and an output arena and
+ * copies every R into the output first.
+ *
+ * All or nothing.  The buffer is the only copy of R, so a stream is validated
+ * completely before its first byte is stored: the whole command chain is
+ * parsed and every command's bounds are checked (encoding.c:111-178), and R's
+ * CRC-64/XZ is checked against the header (main.c:341-356).  Per-stream
+ * status, in this precedence (main.c:335-385):
+ *   DG_ERR_MALFORMED    exactly the streams dg_decode_plan_run calls malformed:
+ *                       magic, framing, an unknown command, a missing payload,
+ *                       dst + len or a COPY's src + len past
+ *                       bsz = max(ref_len, version_size);
+ *   DG_ERR_CAPACITY     bsz > buf_cap (and, with d_delta_offsets, a stream
+ *                       longer than delta_len);
+ *   DG_ERR_UNSUPPORTED  a well-formed standard delta (header flag clear): its
+ *                       COPYs read R while V overwrites it; convert it first
+ *                       (dg_inplace_plan_*);
+ *   DG_ERR_SRC_CRC      the buffer's first ref_len bytes are not the delta's R;
+ *   DG_ERR_DST_CRC      the result does not match dst_crc;
+ * a nonzero incoming d_delta_status[i] is passed on.  ignore_hash skips both
+ * CRC checks.  On every status except DG_OK and DG_ERR_DST_CRC no byte of the
+ * arena is changed and d_out_len[i] = 0.
+ *
+ * Result.  On DG_OK and DG_ERR_DST_CRC bytes [0, version_size) of the buffer
+ * equal the reference's replay (apply.c:271-284: R, zeros up to bsz, then the
+ * commands in stream order with memmove), so a delta that leaves part of a
+ * grown tail uncovered leaves zeros there; d_out_len[i] = version_size.  Bytes
+ * [version_size, ref_len) of a shrinking update are unspecified.  No byte at
+ * or past bsz, and none outside the stream's own region, is written.
+ *
+ * Layout.  d_buf is 16-byte aligned; buf_off may be any value; regions may
+ * touch but not overlap (DG_ERR_INVALID_ARG); a buf_cap, ref_len or delta_len
+ * of 4 GiB or more is DG_ERR_TOO_LARGE; n == 0 is a valid empty plan.  The
+ * delta bytes must not overlap the buffers: the stream is read again while the
+ * buffer is written, and the library cannot check this for device offsets.
+ * With d_delta_offsets (n + 1 entries, as dg_inplace_plan_run writes them)
+ * stream i is d_delta[d_delta_offsets[i] .. d_delta_offsets[i+1]) and delta_len
+ * only bounds its length; with NULL it is exactly delta_len bytes at delta_off.
+ * So dg_encode_plan_run -> dg_inplace_plan_run -> dg_update_plan_run chain on
+ * one stream with no host step.
+ *
+ * A run is one kernel on one stream: no allocation, no host synchronisation.
+ * The plan owns, per stream, 40 bytes of descriptor and at most 64 KiB (about
+ * delta_len / 4) in which the validating pass leaves every command's offset
+ * for the applying pass; a stream of more commands than fit (some 30 000) is
+ * parsed a second time instead.  DG_ERR_NOMEM when it cannot be had.
+ * The kernel lives in dg_update.hsaco beside libdeltagpu.so and is loaded on
+ * first use; DG_ERR_HIP with the path in dg_last_error when it is missing.
+ * Stage timing as for the decode plan: "update" (the kernel, validation and
+ * both CRC checks included) and "total". */
+typedef struct {
+	uint64_t buf_off, buf_cap;      /* stream i's buffer in the arena; holds R_i in its first ref_len bytes */
+	uint64_t ref_len;
+	uint64_t delta_off, delta_len;  /* in-place delta i (with d_delta_offsets: delta_len only bounds it) */
+} dg_update_desc_t;
+typedef struct dg_update_plan dg_update_plan_t;
+
+int dg_update_plan_create(dg_context_t *ctx, const dg_update_desc_t *descs /* host */, uint32_t n,
+                          int ignore_hash, dg_update_plan_t **out);
+int dg_update_plan_run(dg_update_plan_t *plan, uint8_t *d_buf, const uint8_t *d_delta,
+                       const uint64_t *d_delta_offsets, const int32_t *d_delta_status,
+                       uint64_t *d_out_len, int32_t *d_status, void *stream);
+int dg_update_plan_set_timing(dg_update_plan_t *plan, int slots);
+int dg_update_plan_stage_times(dg_update_plan_t *plan, float *ms, const char **names, int n);
+void dg_update_plan_destroy(dg_update_plan_t *plan);
+
+/* Host buffers: bufs[i] (buf_cap[i] bytes, R_i in the first ref_len[i]) is
+ * overwritten with V_i, out_len[i] = version_size; a stream that fails (status[i],
+ * may be NULL) keeps its bytes, except that DG_ERR_DST_CRC leaves the replay's
+ * result.  Returns DG_OK (per-stream failures in status) or the first failure
+ * when status is NULL. */
+int dg_update_batch(dg_context_t *ctx, uint8_t *const *bufs, const size_t *ref_len, const size_t *buf_cap,
+                    const uint8_t *const *delta, const size_t *delta_len, uint32_t n,
+                    int ignore_hash, size_t *out_len, int32_t *status);
 
 /* ── synthetic batch generators (bench / test inputs, on the device) ─────
  * Workload definitions in DESIGN.md ("Synthetic inputs"); the oracle's
