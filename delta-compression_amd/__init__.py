@@ -13,6 +13,9 @@ Names and argument meanings follow the reference's interface for this path:
 * ``decode(R, delta)``              — ``delta decode`` (main.c:323-400).
 * ``UpdatePlan`` / ``update_batch`` — an in-place delta applied in the buffer
   that holds R (apply.c:253-284), validated whole before the first store.
+* ``compose(A, B)`` / ``ComposePlan`` / ``compose_batch`` — delta(R -> V1) and
+  delta(V1 -> V2) joined into delta(R -> V2) without R, V1 or V2 (no reference
+  counterpart; the normal form is stated in ``include/delta_gpu.h``).
 * ``info(delta)``                   — ``delta info`` (main.c:402-425).
 * ``diff`` / ``diff_greedy`` / ``diff_onepass`` / ``diff_correcting``, ``place_commands``,
   ``unplace_commands``, ``encode_delta``, ``decode_delta`` — the command-list
@@ -44,6 +47,8 @@ from ._lib import (  # noqa: F401
     DecodePlan,
     InplacePlan,
     UpdatePlan,
+    ComposeDesc,
+    ComposePlan,
     LIB_PATH,
     LIMIT_ONEPASS_MEMBERS,
     LIMIT_TABLE_POOL_BYTES,
@@ -68,6 +73,8 @@ from ._lib import (  # noqa: F401
     make_inplace,
     make_inplace_batch,
     update_batch,
+    compose,
+    compose_batch,
     output_size,
     place_commands,
     status_string,
@@ -77,6 +84,7 @@ from ._lib import (  # noqa: F401
 __all__ = [
     "ALGO_ONEPASS", "ALGO_CORRECTING", "ALGO_GREEDY", "SEED_LEN", "TABLE_SIZE",
     "MAX_TABLE_SIZE", "BUF_CAP", "Context", "DeltaError", "DiffOptions", "EncodePlan", "DecodePlan", "InplacePlan", "UpdatePlan",
+    "ComposeDesc", "ComposePlan", "compose", "compose_batch",
     "crc64_xz", "decode", "default_context", "encode", "encode_batch", "encode_pipelined", "info", "lib",
     "make_inplace", "make_inplace_batch", "update_batch", "status_string", "LIB_PATH", "LIMIT_TABLE_POOL_BYTES",
     "LIMIT_ONEPASS_MEMBERS", "MEMBERS_AUTO", "MEMBERS_ON", "MEMBERS_OFF",

@@ -84,6 +84,10 @@ class UpdateDesc(C.Structure):   # dg_update_desc_t
                 ("delta_off", C.c_uint64), ("delta_len", C.c_uint64)]
 
 
+class ComposeDesc(C.Structure):   # dg_compose_desc_t
+    _fields_ = [("a_off", C.c_uint64), ("a_cap", C.c_uint64), ("b_off", C.c_uint64), ("b_cap", C.c_uint64)]
+
+
 class InplaceStats(C.Structure):
     _fields_ = [("already_inplace", C.c_int), ("num_copies", C.c_uint64), ("num_adds", C.c_uint64),
                 ("copy_bytes", C.c_uint64), ("add_bytes", C.c_uint64)]
@@ -196,6 +200,15 @@ def _load() -> C.CDLL:
         "dg_update_plan_destroy": (None, [vp]),
         "dg_update_batch": (C.c_int, [vp, C.POINTER(u8p), C.POINTER(sz), C.POINTER(sz), C.POINTER(u8p), C.POINTER(sz),
                                       u32, C.c_int, C.POINTER(sz), C.POINTER(i32)]),
+        "dg_compose": (C.c_int, [u8p, sz, u8p, sz, C.c_int, C.POINTER(Buffer)]),
+        "dg_compose_plan_create": (C.c_int, [vp, C.POINTER(ComposeDesc), u32, C.c_int, C.POINTER(vp)]),
+        "dg_compose_plan_create_for": (C.c_int, [vp, vp, vp, C.c_int, C.POINTER(vp)]),
+        "dg_compose_plan_run": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, u64, vp, vp, vp]),
+        "dg_compose_plan_set_timing": (C.c_int, [vp, C.c_int]),
+        "dg_compose_plan_stage_times": (C.c_int, [vp, C.POINTER(C.c_float), C.POINTER(C.c_char_p), C.c_int]),
+        "dg_compose_plan_destroy": (None, [vp]),
+        "dg_compose_batch": (C.c_int, [vp, C.POINTER(u8p), C.POINTER(sz), C.POINTER(u8p), C.POINTER(sz), u32,
+                                       C.c_int, C.POINTER(Buffer), C.POINTER(i32)]),
         "dg_synth_edit_pairs_device": (C.c_int, [vp, vp, vp, u32, u64, u64, u64, vp]),
         "dg_synth_shift_pairs_device": (C.c_int, [vp, u64, u32, u64, u64, u32, C.POINTER(Pair),
                                                   C.POINTER(u64), C.POINTER(u64), vp, vp, vp]),
@@ -511,6 +524,56 @@ class UpdatePlan:
             pass
 
 
+class ComposePlan:
+    """dg_compose_plan_t: a batch of delta pairs composed on the device,
+    delta(R -> V1) and delta(V1 -> V2) giving delta(R -> V2).  descs: (a_off,
+    a_cap, b_off, b_cap) per pair, or for_plans: the two EncodePlans whose
+    packed outputs the run composes (pass their offsets and statuses to run).
+    A run with d_out = 0 and out_cap = 0 is the sizing run."""
+
+    def __init__(self, ctx: Context, descs: Optional[Sequence[Tuple[int, int, int, int]]] = None,
+                 ignore_hash: bool = False, for_plans: Optional[Tuple["EncodePlan", "EncodePlan"]] = None):
+        self.ctx = ctx
+        h = C.c_void_p()
+        if for_plans is not None:
+            ctx.check(lib.dg_compose_plan_create_for(ctx.handle, for_plans[0].handle, for_plans[1].handle,
+                                                     int(ignore_hash), C.byref(h)), "dg_compose_plan_create_for")
+            self.n = for_plans[0].n
+        else:
+            n = len(descs)
+            arr = (ComposeDesc * max(n, 1))(*[ComposeDesc(*d) for d in descs])
+            ctx.check(lib.dg_compose_plan_create(ctx.handle, arr, n, int(ignore_hash), C.byref(h)),
+                      "dg_compose_plan_create")
+            self.n = n
+        self.handle = h
+
+    def run(self, d_a: int, d_b: int, d_out: int, out_cap: int, d_out_offsets: int, d_status: int,
+            d_a_offsets: int = 0, d_a_status: int = 0, d_b_offsets: int = 0, d_b_status: int = 0, stream: int = 0):
+        self.ctx.check(lib.dg_compose_plan_run(self.handle, d_a, d_a_offsets or None, d_a_status or None,
+                                               d_b, d_b_offsets or None, d_b_status or None, d_out or None, out_cap,
+                                               d_out_offsets, d_status, stream or None), "dg_compose_plan_run")
+
+    def set_timing(self, slots: int = 1):
+        self.ctx.check(lib.dg_compose_plan_set_timing(self.handle, int(slots)), "set_timing")
+
+    def stage_times(self):
+        ms = (C.c_float * 8)()
+        names = (C.c_char_p * 8)()
+        k = lib.dg_compose_plan_stage_times(self.handle, ms, names, 8)
+        return {names[i].decode(): ms[i] for i in range(k)}
+
+    def close(self):
+        if self.handle:
+            lib.dg_compose_plan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def encode(R: bytes, V: bytes, algorithm="onepass", p: int = SEED_LEN, q: int = TABLE_SIZE,
            buf_cap: int = BUF_CAP, max_table: int = MAX_TABLE_SIZE, splay: bool = False,
            inplace: bool = False, policy: str = "localmin",
@@ -656,6 +719,48 @@ def make_inplace_batch(items: Sequence[Tuple[bytes, bytes]], policy: str = "loca
         lib.dg_buffer_free(C.byref(outs[i]))
     if bad is not None:
         raise DeltaError(st[bad], f"delta {bad}")
+    return res
+
+
+def compose(A: bytes, B: bytes, ignore_hash: bool = False) -> bytes:
+    """delta(R -> V1) and delta(V1 -> V2) -> delta(R -> V2) in normal form
+    (dg_compose): host only, and none of R, V1 or V2 is needed."""
+    out = Buffer()
+    rc = lib.dg_compose(_u8(A), len(A), _u8(B), len(B), int(ignore_hash), C.byref(out))
+    if rc:
+        raise DeltaError(rc, "dg_compose")
+    res = C.string_at(out.data, out.len) if out.len else b""
+    lib.dg_buffer_free(C.byref(out))
+    return res
+
+
+def compose_batch(items: Sequence[Tuple[bytes, bytes]], ignore_hash: bool = False,
+                  ctx: Optional[Context] = None, status: bool = False):
+    """(A, B) delta pairs composed on the device in one batch
+    (dg_compose_batch); equal to compose item by item.  Raises DeltaError for
+    the first failing item; with status=True returns (results, statuses)
+    instead, a failed item's result being b""."""
+    ctx = ctx or default_context()
+    n = len(items)
+    if n == 0:
+        return ([], []) if status else []
+    keep = [(bytes(a), bytes(b)) for a, b in items]
+    ap = (C.POINTER(C.c_uint8) * n)(*[_u8(a) for a, _ in keep])
+    bp = (C.POINTER(C.c_uint8) * n)(*[_u8(b) for _, b in keep])
+    al = (C.c_size_t * n)(*[len(a) for a, _ in keep])
+    bl = (C.c_size_t * n)(*[len(b) for _, b in keep])
+    outs = (Buffer * n)()
+    st = (C.c_int32 * n)()
+    ctx.check(lib.dg_compose_batch(ctx.handle, ap, al, bp, bl, n, int(ignore_hash), outs, st), "dg_compose_batch")
+    res = []
+    for i in range(n):
+        res.append(C.string_at(outs[i].data, outs[i].len) if outs[i].len else b"")
+        lib.dg_buffer_free(C.byref(outs[i]))
+    if status:
+        return res, list(st)
+    for i in range(n):
+        if st[i]:
+            raise DeltaError(st[i], f"pair {i}")
     return res
 
 

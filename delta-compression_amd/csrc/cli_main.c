@@ -10,11 +10,14 @@
  *   delta decode <ref> <delta> <output> [--ignore-hash]
  *   delta info <delta>
  *   delta inplace <ref> <delta_in> <delta_out> [--policy localmin|constant]
+ *   delta compose <delta_ab> <delta_bc> <delta_out> [--ignore-hash]
  *
  * --inplace / inplace run the CRWI conversion on the host (dg_make_inplace,
  * main.c:279-283 and :427-480).  --splay applies to greedy only (its tie-break
  * among the longest matches); with onepass or correcting it is not provided
- * by this build (exit 1 with a message).
+ * by this build (exit 1 with a message).  compose joins delta(R -> V1) and
+ * delta(V1 -> V2) into delta(R -> V2) on the host (dg_compose): no GPU and
+ * none of R, V1 or V2.
  */
 #include <errno.h>
 #include <getopt.h>
@@ -89,6 +92,7 @@ static void usage(void)
 	    "  delta decode <ref> <delta> <output> [--ignore-hash]\n"
 	    "  delta info <delta>\n"
 	    "  delta inplace <ref> <delta_in> <delta_out> [--policy P]\n"
+	    "  delta compose <delta_ab> <delta_bc> <delta_out> [--ignore-hash]\n"
 	    "\n"
 	    "Algorithms: greedy, onepass, correcting (MI355X)\n"
 	    "\n"
@@ -338,6 +342,63 @@ static int cmd_inplace(int argc, char **argv)   /* main.c:427-480 */
 	return 0;
 }
 
+static int is_delta_file(const uint8_t *d, size_t dl)
+{
+	return dl >= DG_HEADER_SIZE && memcmp(d, "DLT\x03", 4) == 0;
+}
+
+static int cmd_compose(int argc, char **argv)
+{
+	if (argc < 5) usage();
+	const char *a_path = argv[2], *b_path = argv[3], *out_path = argv[4];
+	int ignore = 0;
+	for (int k = 5; k < argc; k++)
+		if (strcmp(argv[k], "--ignore-hash") == 0) ignore = 1;
+	size_t al, bl;
+	uint8_t *a = read_file(a_path, &al), *b = read_file(b_path, &bl);
+	if (!is_delta_file(a, al) || !is_delta_file(b, bl)) {
+		fprintf(stderr, "delta_compose: not a delta file\n");
+		return 1;
+	}
+	dg_buffer_t o = {0};
+	double t0 = now();
+	int rc = dg_compose(a, al, b, bl, ignore, &o);
+	double t1 = now();
+	if (rc == DG_ERR_SRC_CRC) {
+		fprintf(stderr, "second delta is not against the first delta's output: expected ");
+		hex(stderr, a + 17, 8);
+		fprintf(stderr, ", got ");
+		hex(stderr, b + 9, 8);
+		fprintf(stderr, "\n");
+		return 1;
+	}
+	if (rc == DG_ERR_UNSUPPORTED) {
+		fprintf(stderr, "delta_compose: unsupported input (an in-place delta, or commands not placed in sequence)\n");
+		return 1;
+	}
+	if (rc) {
+		fprintf(stderr, "delta_compose: %s\n", dg_status_string(rc));
+		return 1;
+	}
+	write_file(out_path, o.data, o.len);
+	dg_delta_info_t inf;
+	dg_delta_info(o.data, o.len, &inf);
+	printf("Input delta:  %s (%zu bytes)\n", a_path, al);
+	printf("Input delta:  %s (%zu bytes)\n", b_path, bl);
+	printf("Output delta: %s (%zu bytes)\n", out_path, o.len);
+	printf("Commands:     %llu copies, %llu adds\n", (unsigned long long)inf.num_copies,
+	       (unsigned long long)inf.num_adds);
+	printf("Copy bytes:   %llu\n", (unsigned long long)inf.copy_bytes);
+	printf("Add bytes:    %llu\n", (unsigned long long)inf.add_bytes);
+	printf("Src CRC:      "); hex(stdout, inf.src_crc, 8); printf("\n");
+	printf("Dst CRC:      "); hex(stdout, inf.dst_crc, 8); printf("\n");
+	printf("Time:         %.3fs\n", t1 - t0);
+	dg_buffer_free(&o);
+	free(a);
+	free(b);
+	return 0;
+}
+
 int main(int argc, char **argv)
 {
 	if (argc < 2) usage();
@@ -345,6 +406,7 @@ int main(int argc, char **argv)
 	if (strcmp(argv[1], "decode") == 0) return cmd_decode(argc, argv);
 	if (strcmp(argv[1], "info") == 0) return cmd_info(argc, argv);
 	if (strcmp(argv[1], "inplace") == 0) return cmd_inplace(argc, argv);
+	if (strcmp(argv[1], "compose") == 0) return cmd_compose(argc, argv);
 	usage();
 	return 1;
 }

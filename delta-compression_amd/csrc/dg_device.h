@@ -197,7 +197,7 @@ void plan_options(const dg_encode_plan_t* P, dg_algorithm_t* algo, dg_diff_optio
 void** ctx_inplace(dg_context_t* ctx, void (*release)(void*));
 // the context's slots for code objects loaded at run time, one per module;
 // ctx_inplace is slot kCtxModInplace
-enum : int { kCtxModInplace = 0, kCtxModUpdate = 1, kCtxModules = 2 };
+enum : int { kCtxModInplace = 0, kCtxModUpdate = 1, kCtxModCompose = 2, kCtxModules = 3 };
 void** ctx_module(dg_context_t* ctx, int slot, void (*release)(void*));
 const uint64_t* ctx_crc_tables(const dg_context_t* ctx);     // the CRC tables on the device (CrcArgs::tables)
 int ctx_fail(dg_context_t* ctx, int code, const char* msg);   // records dg_last_error, returns code

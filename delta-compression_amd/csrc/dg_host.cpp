@@ -43,7 +43,8 @@ struct dg_context {
 	void* io = nullptr;                 // dg_encode_pipelined's slots (dg_host_io.cpp)
 	void (*io_free)(void*) = nullptr;
 	// code objects loaded at run time: the in-place conversion module
-	// (dg_inplace_host.cpp), the in-place update module (dg_update_host.cpp)
+	// (dg_inplace_host.cpp), the in-place update module (dg_update_host.cpp),
+	// the composition module (dg_compose_host.cpp)
 	void* module[kCtxModules] = {};
 	void (*module_free[kCtxModules])(void*) = {};
 };

@@ -642,6 +642,136 @@ int dg_update_batch(dg_context_t *ctx, uint8_t *const *bufs, const size_t *ref_l
                     const uint8_t *const *delta, const size_t *delta_len, uint32_t n,
                     int ignore_hash, size_t *out_len, int32_t *status);
 
+/* ── composition: delta(R -> V1) and delta(V1 -> V2) give delta(R -> V2) ──────
+ *
+ * A store keeps R, A = delta(R -> V1) and B = delta(V1 -> V2); a client that
+ * still holds R needs one delta R -> V2.  Composition is a pure transform of
+ * the two command streams: it needs none of R, V1 or V2.  Every byte of V2 is
+ * a literal of B, a literal of A, or a byte of R, and the two command lists
+ * say which.  (The reference has no such function; xdelta's `merge` is the
+ * same step.)
+ *
+ * Inputs.  A and B are standard deltas (header flag clear), B against
+ * V1: |V1| = A.version_size.  Both are sequentially placed exact covers: every
+ * command's dst equals the sum of the earlier lengths and the lengths sum to
+ * the stream's version_size, which every encoder here and
+ * delta_place_commands emit.
+ *
+ * Provenance.  Walk B's commands in order.  An ADD contributes its literal
+ * bytes.  A COPY(s, l) contributes, for each command j of A whose V1 interval
+ * [d_j, d_j + len_j) meets [s, s + l), the overlap [x, y): if j is a COPY,
+ * COPY(src_j + (x - d_j), y - x) from R; if j is an ADD, the literal slice
+ * data_j[x - d_j .. y - d_j).  Zero-length commands contribute nothing.
+ *
+ * Normal form.  The pieces are concatenated and neighbours merged maximally:
+ * consecutive literal pieces become one ADD; consecutive COPY pieces become
+ * one COPY whenever the second starts in R where the first ends; wherever the
+ * neighbours came from (inside one COPY of B, across commands of B, from two
+ * commands of A).  No zero-length command is emitted, dst is sequential, the
+ * header has flag byte 0, version_size = B.version_size, src_crc = A.src_crc,
+ * dst_crc = B.dst_crc, and one END byte closes the stream.  The result is a
+ * function of the byte-provenance map alone (for each position of V2: a
+ * literal, or which offset of R), so compose(compose(A, B), C) ==
+ * compose(A, compose(B, C)) byte for byte, and compose(A, I) with I the
+ * one-COPY identity delta of V1 is A's own normal form.  The host function,
+ * the device path and the tests' Python model produce it byte for byte; it is
+ * an ordinary DLT\x03 standard delta that every decoder here and the
+ * reference's `delta decode` decode to V2 with both CRC checks passing.
+ *
+ * Status, per pair.  The kind of defect decides, not its position in the
+ * stream; first match wins:
+ *   (incoming)          a nonzero d_a_status[i], then d_b_status[i], is passed on;
+ *   DG_ERR_MALFORMED    what dg_inplace_plan_run calls malformed, in either
+ *                       stream (magic, framing, an unknown command, a payload
+ *                       past the end); a COPY of B with src + len >
+ *                       A.version_size; a COPY of A with src + len > 2^32,
+ *                       which no reference of this format satisfies;
+ *   DG_ERR_CAPACITY     (device) a stream longer than its capacity, or more
+ *                       commands than the plan's work memory holds;
+ *   DG_ERR_UNSUPPORTED  either header has the in-place flag; placement is not
+ *                       sequential; the lengths do not sum to version_size;
+ *   DG_ERR_SRC_CRC      A.dst_crc != B.src_crc: B is not a delta against A's
+ *                       output; ignore_hash skips this check;
+ *   DG_ERR_TOO_LARGE    the composed delta would be 4 GiB or more;
+ *   DG_ERR_CAPACITY     (device) the pair's output ends past out_cap.
+ * The composer never sees R: a COPY of A that reads past |R| passes through,
+ * and decode rejects C exactly as it would reject A.  A failed pair's output
+ * is empty and its neighbours are untouched; for a pair that fails on out_cap
+ * the offsets still count its size, as the encode and in-place plans' do.
+ *
+ * dg_compose is pure host code (no context, no GPU): linear in input plus
+ * output, one binary search per COPY of B; *out is malloc'd.  Streams of
+ * 4 GiB or more are DG_ERR_TOO_LARGE. */
+int dg_compose(const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len,
+               int ignore_hash, dg_buffer_t *out);
+
+/* ── composition of a batch on the device ──────────────────────────────────
+ *
+ * The same transform, byte for byte, for N pairs: streams A_i in one device
+ * arena, B_i in another, C_i packed like the encode plan's output at
+ * d_out[d_out_offsets[i] .. d_out_offsets[i+1]), n + 1 offsets.  One wave per
+ * pair maps B's commands onto A's (tables over A's commands, two binary
+ * searches per COPY of B, merges across commands by wave scans), the size scan
+ * packs the outputs, one block per pair writes them.  A run is two kernels and
+ * the scan on one stream: no allocation, no host synchronisation, graph-
+ * capturable like its siblings.  So dg_encode_plan_run (twice) ->
+ * dg_compose_plan_run -> dg_inplace_plan_run -> dg_update_plan_run take a
+ * buffer from R to V2 on one stream with no host step.
+ *
+ * Offsets.  With d_a_offsets (n + 1 entries, as dg_encode_plan_run writes
+ * them) stream A_i is d_a[d_a_offsets[i] .. d_a_offsets[i+1]) and a_cap only
+ * bounds its length; with NULL it is exactly a_cap bytes at a_off.  Likewise
+ * for B.  The d_a, d_b and d_out ranges must not overlap.
+ *
+ * Sizing.  There is no a-priori bound of the output: B may copy one range of
+ * V1 many times, so the piece count can reach |A commands| x |B copies|.
+ * d_out_offsets always receives the true sizes.  A run with d_out = NULL and
+ * out_cap = 0 is the sizing run: every pair that would be DG_OK reports the
+ * out_cap DG_ERR_CAPACITY.
+ *
+ * Work memory is allocated at plan creation from the capacities: (a_cap - 25)
+ * / 9 possible commands of A and (b_cap - 25) / 9 of B (a plan made from two
+ * encode plans uses the encoders' record capacities), 20 bytes per command of
+ * either stream; DG_ERR_NOMEM when it cannot be had.  A capacity of 4 GiB or
+ * more is DG_ERR_TOO_LARGE; n == 0 is a valid empty plan.  In the emit kernel
+ * one lane walks the pieces of one command of B, so a COPY of B that spans
+ * very many commands of A holds its lane for that long.
+ *
+ * The kernels live in dg_compose.hsaco beside libdeltagpu.so and are loaded
+ * on first use; DG_ERR_HIP with the path in dg_last_error when it is missing.
+ * Stage timing as for the in-place plan: "map", "scan", "emit", "total". */
+typedef struct {
+	uint64_t a_off, a_cap;   /* delta(R -> V1) i: start, and most bytes it may have */
+	uint64_t b_off, b_cap;   /* delta(V1 -> V2) i */
+} dg_compose_desc_t;
+typedef struct dg_compose_plan dg_compose_plan_t;
+
+int dg_compose_plan_create(dg_context_t *ctx, const dg_compose_desc_t *descs /* host */,
+                           uint32_t n, int ignore_hash, dg_compose_plan_t **out);
+/* Capacities from two encode plans with equal pair counts: (R, V1) and
+ * (V1, V2); pass dg_encode_plan_run's offsets and statuses to the run. */
+int dg_compose_plan_create_for(dg_context_t *ctx, const dg_encode_plan_t *enc_a,
+                               const dg_encode_plan_t *enc_b, int ignore_hash,
+                               dg_compose_plan_t **out);
+int dg_compose_plan_run(dg_compose_plan_t *plan,
+                        const uint8_t *d_a, const uint64_t *d_a_offsets,
+                        const int32_t *d_a_status,
+                        const uint8_t *d_b, const uint64_t *d_b_offsets,
+                        const int32_t *d_b_status,
+                        uint8_t *d_out, uint64_t out_cap,
+                        uint64_t *d_out_offsets, int32_t *d_status, void *stream);
+int dg_compose_plan_set_timing(dg_compose_plan_t *plan, int slots);
+int dg_compose_plan_stage_times(dg_compose_plan_t *plan, float *ms,
+                                const char **names, int n);
+void dg_compose_plan_destroy(dg_compose_plan_t *plan);
+
+/* Host buffers in, host buffers out (outs[i] malloc'd, status[i] may be
+ * NULL): the sizing run, then the real run.  Returns DG_OK (per-pair failures
+ * in status) or the first failure when status is NULL. */
+int dg_compose_batch(dg_context_t *ctx, const uint8_t *const *a, const size_t *a_len,
+                     const uint8_t *const *b, const size_t *b_len, uint32_t n,
+                     int ignore_hash, dg_buffer_t *outs, int32_t *status);
+
 /* ── synthetic batch generators (bench / test inputs, on the device) ─────
  * Workload definitions in DESIGN.md ("Synthetic inputs"); the oracle's
  * or_synth_* functions produce the same bytes on the CPU. */
