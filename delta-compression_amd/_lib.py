@@ -306,12 +306,42 @@ def default_context() -> Context:
         return _default_ctx
 
 
-class EncodePlan:
+class _Plan:
+    """What the plan classes share: the handle's lifetime and the stage timing
+    of dg_<_prefix>_set_timing / _stage_times / _destroy."""
+
+    _prefix = ""   # the plan's C function prefix, e.g. "dg_encode_plan"
+    handle = None
+
+    def set_timing(self, slots: int = 1):
+        self.ctx.check(getattr(lib, self._prefix + "_set_timing")(self.handle, int(slots)), "set_timing")
+
+    def stage_times(self):
+        ms = (C.c_float * 8)()
+        names = (C.c_char_p * 8)()
+        k = getattr(lib, self._prefix + "_stage_times")(self.handle, ms, names, 8)
+        return {names[i].decode(): ms[i] for i in range(k)}
+
+    def close(self):
+        if self.handle:
+            getattr(lib, self._prefix + "_destroy")(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class EncodePlan(_Plan):
     """Device-resident batch (dg_encode_plan_t): fixed pair geometry + options.
 
     ``pairs`` is a sequence of (r_off, r_len, v_off, v_len) into two device
     arenas.  ``run`` takes device addresses and an optional stream handle.
     """
+
+    _prefix = "dg_encode_plan"
 
     def __init__(self, ctx: Context, algorithm, pairs: Sequence[Tuple[int, int, int, int]],
                  **opt_kw):
@@ -360,12 +390,6 @@ class EncodePlan:
         _set_every(getattr(lib, "dg_encode_plan_set_timing_every", None), self, every)
         self.ctx.check(lib.dg_encode_plan_set_timing(self.handle, int(slots)), "set_timing")
 
-    def stage_times(self):
-        ms = (C.c_float * 8)()
-        names = (C.c_char_p * 8)()
-        k = lib.dg_encode_plan_stage_times(self.handle, ms, names, 8)
-        return {names[i].decode(): ms[i] for i in range(k)}
-
     def copy_counts_ptr(self) -> int:
         return lib.dg_encode_plan_copy_counts_device(self.handle) or 0
 
@@ -374,20 +398,11 @@ class EncodePlan:
         self.ctx.check(lib.dg_encode_plan_run(self.handle, d_ref, d_ver, d_out, out_cap, d_offsets,
                                               d_status, stream or None), "dg_encode_plan_run")
 
-    def close(self):
-        if getattr(self, "handle", None):
-            lib.dg_encode_plan_destroy(self.handle)
-            self.handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class DecodePlan:
+class DecodePlan(_Plan):
     """dg_decode_plan_t: batched device decode + CRC verify (C5)."""
+
+    _prefix = "dg_decode_plan"
 
     def __init__(self, ctx: Context, descs: Sequence[Tuple[int, int, int, int, int, int]],
                  ignore_hash: bool = False):
@@ -410,29 +425,14 @@ class DecodePlan:
         _set_every(getattr(lib, "dg_decode_plan_set_timing_every", None), self, every)
         self.ctx.check(lib.dg_decode_plan_set_timing(self.handle, int(slots)), "set_timing")
 
-    def stage_times(self):
-        ms = (C.c_float * 8)()
-        names = (C.c_char_p * 8)()
-        k = lib.dg_decode_plan_stage_times(self.handle, ms, names, 8)
-        return {names[i].decode(): ms[i] for i in range(k)}
 
-    def close(self):
-        if self.handle:
-            lib.dg_decode_plan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class InplacePlan:
+class InplacePlan(_Plan):
     """dg_inplace_plan_t: a batch of standard deltas converted to in-place form
     on the device.  descs: (ref_off, ref_len, delta_off, delta_cap) per delta, or
     for_plan: an EncodePlan whose packed output the run converts (pass its
     offsets and status to run)."""
+
+    _prefix = "dg_inplace_plan"
 
     def __init__(self, ctx: Context, descs: Optional[Sequence[Tuple[int, int, int, int]]] = None,
                  policy: str = "localmin", for_plan: Optional["EncodePlan"] = None):
@@ -460,32 +460,14 @@ class InplacePlan:
                                                d_delta_status or None, d_out, out_cap, d_out_offsets, d_status,
                                                stream or None), "dg_inplace_plan_run")
 
-    def set_timing(self, slots: int = 1):
-        self.ctx.check(lib.dg_inplace_plan_set_timing(self.handle, int(slots)), "set_timing")
 
-    def stage_times(self):
-        ms = (C.c_float * 8)()
-        names = (C.c_char_p * 8)()
-        k = lib.dg_inplace_plan_stage_times(self.handle, ms, names, 8)
-        return {names[i].decode(): ms[i] for i in range(k)}
-
-    def close(self):
-        if self.handle:
-            lib.dg_inplace_plan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class UpdatePlan:
+class UpdatePlan(_Plan):
     """dg_update_plan_t: a batch of in-place deltas applied in place on the
     device: each stream's buffer, which holds R, becomes V.  descs: (buf_off,
     buf_cap, ref_len, delta_off, delta_len) per stream.  A stream that fails
     validation (status other than 0 and 10) keeps every byte."""
+
+    _prefix = "dg_update_plan"
 
     def __init__(self, ctx: Context, descs: Sequence[Tuple[int, int, int, int, int]], ignore_hash: bool = False):
         self.ctx = ctx
@@ -503,33 +485,15 @@ class UpdatePlan:
                                               d_delta_status or None, d_out_len, d_status, stream or None),
                        "dg_update_plan_run")
 
-    def set_timing(self, slots: int = 1):
-        self.ctx.check(lib.dg_update_plan_set_timing(self.handle, int(slots)), "set_timing")
 
-    def stage_times(self):
-        ms = (C.c_float * 8)()
-        names = (C.c_char_p * 8)()
-        k = lib.dg_update_plan_stage_times(self.handle, ms, names, 8)
-        return {names[i].decode(): ms[i] for i in range(k)}
-
-    def close(self):
-        if self.handle:
-            lib.dg_update_plan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class ComposePlan:
+class ComposePlan(_Plan):
     """dg_compose_plan_t: a batch of delta pairs composed on the device,
     delta(R -> V1) and delta(V1 -> V2) giving delta(R -> V2).  descs: (a_off,
     a_cap, b_off, b_cap) per pair, or for_plans: the two EncodePlans whose
     packed outputs the run composes (pass their offsets and statuses to run).
     A run with d_out = 0 and out_cap = 0 is the sizing run."""
+
+    _prefix = "dg_compose_plan"
 
     def __init__(self, ctx: Context, descs: Optional[Sequence[Tuple[int, int, int, int]]] = None,
                  ignore_hash: bool = False, for_plans: Optional[Tuple["EncodePlan", "EncodePlan"]] = None):
@@ -552,26 +516,6 @@ class ComposePlan:
         self.ctx.check(lib.dg_compose_plan_run(self.handle, d_a, d_a_offsets or None, d_a_status or None,
                                                d_b, d_b_offsets or None, d_b_status or None, d_out or None, out_cap,
                                                d_out_offsets, d_status, stream or None), "dg_compose_plan_run")
-
-    def set_timing(self, slots: int = 1):
-        self.ctx.check(lib.dg_compose_plan_set_timing(self.handle, int(slots)), "set_timing")
-
-    def stage_times(self):
-        ms = (C.c_float * 8)()
-        names = (C.c_char_p * 8)()
-        k = lib.dg_compose_plan_stage_times(self.handle, ms, names, 8)
-        return {names[i].decode(): ms[i] for i in range(k)}
-
-    def close(self):
-        if self.handle:
-            lib.dg_compose_plan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def encode(R: bytes, V: bytes, algorithm="onepass", p: int = SEED_LEN, q: int = TABLE_SIZE,

@@ -34,32 +34,12 @@
 #include "dg_compose_dev.h"
 #include "dg_devutil.h"
 #include "dg_parse_chain.h"
+#include "dg_stream_dev.h"
 
 using namespace dg;
 using namespace dgcp;
 
 namespace {
-
-typedef uint32_t u32x4_u __attribute__((ext_vector_type(4), aligned(1)));
-
-constexpr uint32_t kSmallCopy = 64;   // emit: spans up to this many bytes are one thread's
-
-// orders LDS and global memory between the lanes of the (one-wave) block
-__device__ __forceinline__ void wave_sync() {
-	__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-	__builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ uint32_t be32_at(const uint8_t* p) {
-	return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
-}
-
-// exclusive prefix of x over the wave as 64 bits, and the wave's total
-__device__ __forceinline__ uint64_t wave_excl_scan64(uint32_t x, uint64_t* total) {
-	const uint32_t lo = wave_incl_scan(x & 0xFFFFu), hi = wave_incl_scan(x >> 16);
-	*total = ((uint64_t)rdlane(hi, 63) << 16) + rdlane(lo, 63);
-	return ((uint64_t)hi << 16) + lo - x;
-}
 
 // 1 + the nearest earlier lane whose flag is set, 0 when there is none
 __device__ __forceinline__ uint32_t prev_set(bool f, uint32_t lane) {
@@ -108,27 +88,6 @@ __device__ __forceinline__ uint32_t lower(const uint32_t* t, uint32_t lo, uint32
 		else hi = mid;
 	}
 	return lo;
-}
-
-// one command's fields, decoded from the parser's window by its lane
-struct Hdr {
-	uint32_t cx, kind, src, dst, len;
-};
-__device__ __forceinline__ Hdr decode_hdr(const uint8_t* win, const uint16_t* cmds, uint32_t k, bool mine) {
-	Hdr h{0, 0, 0, 0, 0};
-	if (mine) {
-		h.cx = cmds[k];
-		h.kind = win[h.cx];
-		if (h.kind == 1) {
-			h.src = be32_at(win + h.cx + 1);
-			h.dst = be32_at(win + h.cx + 5);
-			h.len = be32_at(win + h.cx + 9);
-		} else {
-			h.dst = be32_at(win + h.cx + 1);
-			h.len = be32_at(win + h.cx + 5);
-		}
-	}
-	return h;
 }
 
 }  // namespace
@@ -378,26 +337,6 @@ extern "C" __global__ __launch_bounds__(64) void dg_compose_map_kernel(CpArgs a)
 	}
 	finish(0, size);
 }
-
-namespace {
-
-// n bytes by one wave; src and dst do not overlap
-__device__ __forceinline__ void wave_copy(uint8_t* dst, const uint8_t* src, uint32_t n, uint32_t lane) {
-	const uint32_t n16 = n >> 4;
-	for (uint32_t j = lane; j < n16; j += 64)
-		*reinterpret_cast<u32x4_u*>(dst + 16 * j) = *reinterpret_cast<const u32x4_u*>(src + 16 * j);
-	const uint32_t t = 16 * n16 + lane;
-	if (t < n) dst[t] = src[t];
-}
-
-__device__ __forceinline__ void put_be32(uint8_t* p, uint32_t x) {
-	p[0] = (uint8_t)(x >> 24);
-	p[1] = (uint8_t)(x >> 16);
-	p[2] = (uint8_t)(x >> 8);
-	p[3] = (uint8_t)x;
-}
-
-}  // namespace
 
 extern "C" __global__ __launch_bounds__(256) void dg_compose_emit_kernel(CpArgs a) {
 	const uint32_t i = blockIdx.x;

@@ -6,6 +6,7 @@
 // on the run stream and one side stream.  The host-memory entry points are in
 // dg_host_io.cpp.  There is no CPU compute fallback: without a GPU every
 // entry point fails with DG_ERR_NO_DEVICE.
+#include <dlfcn.h>
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,6 +19,7 @@
 
 #include "../../include/delta_gpu.h"
 #include "dg_device.h"
+#include "dg_hostutil.h"
 #include "dg_plan.h"
 
 using namespace dg;
@@ -61,8 +63,6 @@ void** dg::ctx_module(dg_context_t* ctx, int slot, void (*release)(void*)) {
 	ctx->module_free[slot] = release;
 	return &ctx->module[slot];
 }
-
-void** dg::ctx_inplace(dg_context_t* ctx, void (*release)(void*)) { return ctx_module(ctx, kCtxModInplace, release); }
 
 const uint64_t* dg::ctx_crc_tables(const dg_context_t* ctx) { return ctx->d_crc_tables; }
 
@@ -205,27 +205,58 @@ const char* dg::ab_env(const char* name) {
 #endif
 }
 
-// ───────────────────────────── device buffers ─────────────────────────────
+// ───────────────────── code objects loaded at run time ────────────────────
 
 namespace {
 
-struct DevBuf {
-	void* p = nullptr;
-	size_t n = 0;
-	~DevBuf() { if (p) hipFree(p); }
-	void release() {
-		if (p) hipFree(p);
-		p = nullptr;
-		n = 0;
-	}
-	int alloc(size_t bytes) {
-		if (p) { hipFree(p); p = nullptr; }
-		n = bytes;
-		if (bytes == 0) return 0;
-		return hipMalloc(&p, bytes) == hipSuccess ? 0 : -1;
-	}
-	template <class T> T* as() const { return static_cast<T*>(p); }
+struct CodeObject {
+	hipModule_t mod = nullptr;
+	std::vector<hipFunction_t> fn;
 };
+
+void code_object_release(void* p) {
+	auto* m = static_cast<CodeObject*>(p);
+	if (m->mod) hipModuleUnload(m->mod);
+	delete m;
+}
+
+// `file` in the directory this library was loaded from
+std::string beside_library(const char* file) {
+	Dl_info info{};
+	if (!dladdr(reinterpret_cast<const void*>(&code_object_release), &info) || !info.dli_fname) return file;
+	std::string p = info.dli_fname;
+	const size_t slash = p.rfind('/');
+	p = slash == std::string::npos ? std::string() : p.substr(0, slash + 1);
+	return p + file;
+}
+
+}  // namespace
+
+int dg::load_kernels(dg_context_t* ctx, int slot, const char* file, const char* label, const char* const* names,
+                     int n_names, const hipFunction_t** fns) {
+	void** held = ctx_module(ctx, slot, code_object_release);
+	if (!*held) {
+		auto* m = new (std::nothrow) CodeObject();
+		if (!m) return DG_ERR_NOMEM;
+		m->fn.assign(n_names, nullptr);
+		const std::string path = beside_library(file);
+		hipError_t e = hipModuleLoad(&m->mod, path.c_str());
+		for (int k = 0; k < n_names && e == hipSuccess; ++k) e = hipModuleGetFunction(&m->fn[k], m->mod, names[k]);
+		if (e != hipSuccess) {
+			(void)hipGetLastError();
+			const std::string msg = std::string(label) + ": cannot load " + path + ": " + hipGetErrorString(e);
+			code_object_release(m);
+			return ctx_fail(ctx, DG_ERR_HIP, msg.c_str());
+		}
+		*held = m;
+	}
+	*fns = static_cast<CodeObject*>(*held)->fn.data();
+	return DG_OK;
+}
+
+// ───────────────────────────── device buffers ─────────────────────────────
+
+namespace {
 
 // one u32 of mapped, coherent host memory the device writes (h: host address,
 // d: its device address)
@@ -251,58 +282,6 @@ struct HostWord {
 		return 0;
 	}
 	uint32_t read() const { return __atomic_load_n(h, __ATOMIC_RELAXED); }
-};
-
-// Stage timing of a plan: `slots` sets of `per_run` events, one set per
-// timed run (a ring); ev holds ev_sets >= slots sets (never shrunk, only the
-// ring is).  The caller has the plan's device current.
-struct TimingRing {
-	std::vector<hipEvent_t> ev;
-	uint32_t per_run = 0;
-	uint32_t slots = 0, runs = 0, ev_sets = 0;
-	uint32_t every = 1, calls = 0;   // events on every `every`-th run (dg_*_plan_set_timing_every)
-	bool timing = false;
-	~TimingRing() {
-		for (auto& e : ev)
-			if (e) hipEventDestroy(e);
-	}
-	// false: an event could not be created (timing is then off)
-	bool set(uint32_t n_slots, uint32_t events_per_run) {
-		if (n_slots > ev_sets) {
-			for (auto& e : ev) hipEventDestroy(e);
-			ev.assign((size_t)events_per_run * n_slots, nullptr);
-			per_run = events_per_run;
-			ev_sets = slots = 0;
-			for (auto& e : ev)
-				// timing only: no system-scope fence when the event is recorded
-				// (a cache writeback + invalidate per event slowed the timed
-				// steps by 15 %: C2 0.335 -> 0.391 ms with two events per step)
-				if (hipEventCreateWithFlags(&e, hipEventDisableSystemFence) != hipSuccess) {
-					e = nullptr;
-					timing = false;
-					return false;
-				}
-			ev_sets = n_slots;
-		}
-		// the ring is exactly `slots` runs long, so stage_times averages the
-		// last `slots` runs even after a longer ring was set before
-		slots = n_slots;
-		timing = n_slots > 0;
-		runs = calls = 0;
-		return true;
-	}
-	void set_every(uint32_t n) {
-		every = n;
-		calls = 0;
-	}
-	// the event set this run records, or nullptr (timing off, or not this run's turn)
-	hipEvent_t* next() {
-		if (!timing || calls++ % every != 0) return nullptr;
-		return &ev[(size_t)per_run * (runs++ % slots)];
-	}
-	// recorded sets to average over, and set s of them
-	uint32_t used() const { return slots ? std::min(runs, slots) : 0; }
-	hipEvent_t* set_at(uint32_t s) { return &ev[(size_t)per_run * s]; }
 };
 
 }  // namespace
@@ -1055,19 +1034,8 @@ int dg_decode_plan_set_timing(dg_decode_plan_t* P, int slots) {
 
 // one stage, "decode": the kernel parses, applies and checks both CRCs
 int dg_decode_plan_stage_times(dg_decode_plan_t* P, float* ms, const char** names, int n) {
-	const uint32_t used = P ? P->ring.used() : 0;
-	if (!used || n < 1) return 0;
-	double acc = 0;
-	for (uint32_t s = 0; s < used; ++s) {
-		hipEvent_t* e = P->ring.set_at(s);
-		if (hipEventSynchronize(e[1]) != hipSuccess) return 0;
-		float t = 0;
-		hipEventElapsedTime(&t, e[0], e[1]);
-		acc += t;
-	}
-	if (ms) ms[0] = (float)(acc / used);
-	if (names) names[0] = "decode";
-	return 1;
+	static const char* const kNames[] = {"decode", "total"};
+	return P ? P->ring.stage_times(kNames, ms, names, std::min(n, 1)) : 0;
 }
 
 int dg_decode_plan_set_timing_every(dg_decode_plan_t* P, int every) {
@@ -1135,11 +1103,6 @@ int dg_decode_plan_run(dg_decode_plan_t* P, const uint8_t* d_ref, const uint8_t*
 	return DG_OK;
 }
 
-void dg_decode_plan_destroy(dg_decode_plan_t* P) {
-	if (!P) return;
-	hipSetDevice(P->ctx->device);
-	hipStreamSynchronize(P->ctx->stream);
-	delete P;
-}
+void dg_decode_plan_destroy(dg_decode_plan_t* P) { plan_destroy(P); }
 
 }  // extern "C"

@@ -14,6 +14,7 @@
 
 #include "../../include/delta_gpu.h"
 #include "dg_device.h"
+#include "dg_hostutil.h"
 #include "dg_plan.h"
 
 namespace {
@@ -60,7 +61,7 @@ int dg_encode_batch(dg_context_t* ctx, dg_algorithm_t algo, const uint8_t* const
 		std::vector<int32_t> st(n, 0);
 		int rc = dg_encode_batch(ctx, algo, r, r_len, v, v_len, n, &o, outs, st.data());
 		if (rc) return rc;
-		int first_bad = DG_OK;
+		dg::BatchStatus bs{status};
 		for (uint32_t i = 0; i < n; ++i) {
 			if (st[i] == DG_OK && outs[i].data) {
 				dg_buffer_t ip{nullptr, 0};
@@ -68,10 +69,9 @@ int dg_encode_batch(dg_context_t* ctx, dg_algorithm_t algo, const uint8_t* const
 				free(outs[i].data);
 				outs[i] = ip;
 			}
-			if (status) status[i] = st[i];
-			if (st[i] && !first_bad) first_bad = st[i];
+			bs.set(i, st[i]);
 		}
-		return status ? DG_OK : first_bad;
+		return bs.result();
 	}
 	hipStream_t st = (hipStream_t)dg_context_stream(ctx);
 
@@ -88,76 +88,56 @@ int dg_encode_batch(dg_context_t* ctx, dg_algorithm_t algo, const uint8_t* const
 	const uint64_t bound = dg_encode_plan_output_bound(plan);
 
 	const bool verbose = opts && ((opts->flags >> DG_OPT_VERBOSE) & 1);
-	Pinned h_in, h_off, h_st;
+	Pinned h_in, h_off, h_st, h_out;
 	Dev d_ref, d_ver, d_out, d_off, d_st, d_stats;
 	std::vector<uint64_t> stats;
+	// (after the buffers: the plan is destroyed, and the stream waited for,
+	// before they are freed)
+	dg::ScopeExit guard([&] { dg_encode_plan_destroy(plan); });
 	if (verbose) {   // the reference's diagnostics (dg_encode_plan_set_stats)
-		if (!d_stats.alloc(64ull * n) || hipMemsetAsync(d_stats.p, 0, 64ull * n, st) != hipSuccess) {
-			dg_encode_plan_destroy(plan);
-			return DG_ERR_NOMEM;
-		}
+		if (!d_stats.alloc(64ull * n) || hipMemsetAsync(d_stats.p, 0, 64ull * n, st) != hipSuccess) return DG_ERR_NOMEM;
 		dg_encode_plan_set_stats(plan, d_stats.as<uint64_t>());
 		stats.assign(8ull * n, 0);
 	}
-	rc = DG_ERR_NOMEM;
 	if (!h_in.alloc(rt + vt) || !h_off.alloc(8ull * (n + 1)) || !h_st.alloc(4ull * n) ||
 	    !d_ref.alloc(rt) || !d_ver.alloc(vt) || !d_out.alloc(bound) ||
-	    !d_off.alloc(8ull * (n + 1)) || !d_st.alloc(4ull * n)) {
-		dg_encode_plan_destroy(plan);
-		return rc;
-	}
+	    !d_off.alloc(8ull * (n + 1)) || !d_st.alloc(4ull * n))
+		return DG_ERR_NOMEM;
 	uint8_t* hr = h_in.as<uint8_t>();
 	uint8_t* hv = hr + rt;
 	for (uint32_t i = 0; i < n; ++i) {
 		if (r_len[i]) memcpy(hr + pairs[i].r_off, r[i], r_len[i]);
 		if (v_len[i]) memcpy(hv + pairs[i].v_off, v[i], v_len[i]);
 	}
-	rc = DG_ERR_HIP;
 	if (hipMemcpyAsync(d_ref.p, hr, rt, hipMemcpyHostToDevice, st) != hipSuccess ||
-	    hipMemcpyAsync(d_ver.p, hv, vt, hipMemcpyHostToDevice, st) != hipSuccess) {
-		dg_encode_plan_destroy(plan);
-		return rc;
-	}
+	    hipMemcpyAsync(d_ver.p, hv, vt, hipMemcpyHostToDevice, st) != hipSuccess)
+		return DG_ERR_HIP;
 	rc = dg_encode_plan_run(plan, d_ref.as<uint8_t>(), d_ver.as<uint8_t>(), d_out.as<uint8_t>(),
 	                        bound, d_off.as<uint64_t>(), d_st.as<int32_t>(), st);
-	if (rc) { dg_encode_plan_destroy(plan); return rc; }
+	if (rc) return rc;
 	if (hipMemcpyAsync(h_off.p, d_off.p, 8ull * (n + 1), hipMemcpyDeviceToHost, st) != hipSuccess ||
 	    hipMemcpyAsync(h_st.p, d_st.p, 4ull * n, hipMemcpyDeviceToHost, st) != hipSuccess ||
-	    hipStreamSynchronize(st) != hipSuccess) {
-		dg_encode_plan_destroy(plan);
+	    hipStreamSynchronize(st) != hipSuccess)
 		return DG_ERR_HIP;
-	}
 	const uint64_t* off = h_off.as<uint64_t>();
 	const uint64_t total = off[n];
-	Pinned h_out;
 	if (!h_out.alloc(total) ||
 	    hipMemcpyAsync(h_out.p, d_out.p, total, hipMemcpyDeviceToHost, st) != hipSuccess ||
 	    (verbose && hipMemcpyAsync(stats.data(), d_stats.p, 64ull * n, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-	    hipStreamSynchronize(st) != hipSuccess) {
-		dg_encode_plan_destroy(plan);
+	    hipStreamSynchronize(st) != hipSuccess)
 		return DG_ERR_HIP;
-	}
 	if (verbose)
 		for (uint32_t i = 0; i < n; ++i)
 			if (h_st.as<int32_t>()[i] == DG_OK)
 				dg::print_verbose(algo, *opts, pairs[i], dg::plan_pp(plan)[i], stats.data() + 8ull * i,
 				                  h_out.as<uint8_t>() + off[i], off[i + 1] - off[i]);
-	dg_encode_plan_destroy(plan);
-	int first_bad = DG_OK;
+	dg::BatchStatus bs{status};
 	for (uint32_t i = 0; i < n; ++i) {
 		const int32_t s = h_st.as<int32_t>()[i];
-		if (status) status[i] = s;
-		if (s != DG_OK) {
-			if (!first_bad) first_bad = s;
-			continue;
-		}
-		const uint64_t len = off[i + 1] - off[i];
-		outs[i].data = (uint8_t*)malloc(len ? len : 1);
-		if (!outs[i].data) return DG_ERR_NOMEM;
-		memcpy(outs[i].data, h_out.as<uint8_t>() + off[i], len);
-		outs[i].len = len;
+		bs.set(i, s);
+		if (s == DG_OK && !dg::buffer_copy(&outs[i], h_out.as<uint8_t>() + off[i], off[i + 1] - off[i])) return DG_ERR_NOMEM;
 	}
-	return status ? DG_OK : first_bad;
+	return bs.result();
 }
 
 // ── pipelined host-to-host encode ──────────────────────────────────────
@@ -338,7 +318,7 @@ int dg_encode_pipelined_multi(dg_context_t* const* ctxs, uint32_t n_ctx, dg_algo
 		uint64_t bound = 0;
 		for (uint32_t i = r.lo; i < r.hi; ++i) {
 			const uint64_t vl = pairs[i].v_len;
-			bound += algo == DG_ALGO_CORRECTING ? 57 + vl + 22 * (vl / p) : 35 + vl + (vl / p) * (p < 22 ? 22 - p : 0);
+			bound += dg::pair_out_bound(algo, p, vl);
 			if ((o.flags >> DG_OPT_INPLACE) & 1) bound += vl;   // COPYs turned into ADD payload
 		}
 		try {
@@ -888,9 +868,5 @@ extern "C" int dg_decode(dg_context_t* ctx, const uint8_t* r, size_t r_len, cons
 	if (vsize && (hipMemcpyAsync(h_o.p, d_o.p, vsize, hipMemcpyDeviceToHost, st) != hipSuccess ||
 	              hipStreamSynchronize(st) != hipSuccess))
 		return DG_ERR_HIP;
-	out->data = (uint8_t*)malloc(vsize ? vsize : 1);
-	if (!out->data) return DG_ERR_NOMEM;
-	if (vsize) memcpy(out->data, h_o.p, vsize);
-	out->len = vsize;
-	return s;
+	return dg::buffer_copy(out, h_o.as<uint8_t>(), vsize) ? s : DG_ERR_NOMEM;
 }

@@ -31,35 +31,17 @@
 #include "dg_inplace_core.h"
 #include "dg_inplace_dev.h"
 #include "dg_parse_chain.h"
+#include "dg_stream_dev.h"
 
 using namespace dg;
 using namespace dgip;
 
 namespace {
 
-typedef uint32_t u32x4_u __attribute__((ext_vector_type(4), aligned(1)));
 typedef uint32_t u32_u __attribute__((aligned(1)));
 
 constexpr uint32_t kLdsWords = 2048;       // dst column cache; radix counters; small graph / ready bitmap
 constexpr uint32_t kSmallGraph = 128;      // copies up to which the Kahn loop and the stall code run out of LDS
-constexpr uint32_t kSmallCopy = 64;        // emit: spans up to this many bytes are one thread's
-
-// orders LDS and global memory between the lanes of the (one-wave) block
-__device__ __forceinline__ void wave_sync() {
-	__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-	__builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ uint32_t be32_at(const uint8_t* p) {
-	return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
-}
-
-// exclusive prefix of x over the wave as 64 bits, and the wave's total
-__device__ __forceinline__ uint64_t wave_excl_scan64(uint32_t x, uint64_t* total) {
-	const uint32_t lo = wave_incl_scan(x & 0xFFFFu), hi = wave_incl_scan(x >> 16);
-	*total = ((uint64_t)rdlane(hi, 63) << 16) + rdlane(lo, 63);
-	return ((uint64_t)hi << 16) + lo - x;
-}
 
 struct WorkPtrs {
 	uint32_t *src, *dst, *len, *a, *b, *indeg, *rank, *byrank, *order;
@@ -281,6 +263,8 @@ extern "C" __global__ __launch_bounds__(64) void dg_inplace_order_kernel(IpArgs 
 		const uint32_t cnt = cw.cnt;
 		for (uint32_t b0 = 0; b0 < cnt; b0 += 64) {
 			const bool mine = b0 + lane < cnt;
+			// (decode_hdr of dg_stream_dev.h, written out: calling it here changes
+			// the instructions the compiler emits for this kernel)
 			uint32_t cx = 0, kind = 0, c_src = 0, c_dst = 0, c_len = 0;
 			if (mine) {
 				cx = cmds[b0 + lane];
@@ -440,26 +424,6 @@ extern "C" __global__ __launch_bounds__(64) void dg_inplace_order_kernel(IpArgs 
 	res.victims = nv;
 	finish(0, 25 + 13ull * kept + res.add_bytes + vict_bytes + 1);
 }
-
-namespace {
-
-// n bytes by one wave; src and dst do not overlap
-__device__ __forceinline__ void wave_copy(uint8_t* dst, const uint8_t* src, uint32_t n, uint32_t lane) {
-	const uint32_t n16 = n >> 4;
-	for (uint32_t j = lane; j < n16; j += 64)
-		*reinterpret_cast<u32x4_u*>(dst + 16 * j) = *reinterpret_cast<const u32x4_u*>(src + 16 * j);
-	const uint32_t t = 16 * n16 + lane;
-	if (t < n) dst[t] = src[t];
-}
-
-__device__ __forceinline__ void put_be32(uint8_t* p, uint32_t x) {
-	p[0] = (uint8_t)(x >> 24);
-	p[1] = (uint8_t)(x >> 16);
-	p[2] = (uint8_t)(x >> 8);
-	p[3] = (uint8_t)x;
-}
-
-}  // namespace
 
 extern "C" __global__ __launch_bounds__(256) void dg_inplace_emit_kernel(IpArgs a) {
 	const uint32_t i = blockIdx.x;

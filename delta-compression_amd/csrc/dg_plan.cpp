@@ -240,6 +240,16 @@ bool members_wanted(const PlanEnv& env, const dg_pair_t* pairs, uint32_t n) {
 
 }  // namespace
 
+// onepass: every COPY covers >= p bytes, so
+//   delta <= 35 + |V| + (|V|/p) * max(0, 22 - p);
+// correcting: a tail-corrected COPY may be shorter than p, but there
+// are at most |V|/p + 1 of them, each with at most one ADD header
+// (greedy: as onepass)
+uint64_t pair_out_bound(dg_algorithm_t algo, uint64_t p, uint64_t v_len) {
+	if (algo != DG_ALGO_CORRECTING) return 35 + v_len + (v_len / p) * (p < 22 ? 22 - p : 0);
+	return 57 + v_len + 22 * (v_len / p);
+}
+
 int encode_geometry(dg_algorithm_t algo, const dg_diff_options_t& o, const dg_pair_t* pairs, uint32_t n,
                     const PlanEnv& env, EncodeGeometry& g, std::string& err) {
 	if (algo != DG_ALGO_GREEDY && algo != DG_ALGO_ONEPASS && algo != DG_ALGO_CORRECTING)
@@ -309,15 +319,7 @@ int encode_geometry(dg_algorithm_t algo, const dg_diff_options_t& o, const dg_pa
 		x.rec_base = rec;
 		x.rec_cap = (uint32_t)(d.v_len / p + 1);
 		rec += x.rec_cap;
-		// onepass: every COPY covers >= p bytes, so
-		//   delta <= 35 + |V| + (|V|/p) * max(0, 22 - p);
-		// correcting: a tail-corrected COPY may be shorter than p, but there
-		// are at most |V|/p + 1 of them, each with at most one ADD header
-		// (greedy: as onepass)
-		if (algo != DG_ALGO_CORRECTING)
-			bound += 35 + d.v_len + (d.v_len / p) * (p < 22 ? 22 - p : 0);
-		else
-			bound += 57 + d.v_len + 22 * (d.v_len / p);
+		bound += pair_out_bound(algo, p, d.v_len);
 		g.qmax = std::max<uint64_t>(g.qmax, x.q);
 		g.qmin = std::min<uint64_t>(g.qmin, x.q);
 		g.v_total += d.v_len;
@@ -551,6 +553,95 @@ void print_verbose(dg_algorithm_t algo, const dg_diff_options_t& o, const dg_pai
 	        (unsigned long long)mt, ck > 0 ? (double)mt / ck * 100.0 : 0.0, (unsigned long long)fpm,
 	        (unsigned long long)bm);
 	print_command_stats(cmds);
+}
+
+// ── in-place and compose plans: descriptors, work memory, bounds ──
+
+namespace {
+
+// descs with max_copies and max_adds filled; extra[i]: the version bytes
+// delta i's COPYs can turn into ADD payload
+int inplace_finish(const std::vector<uint64_t>& extra, InplaceGeometry& g, std::string& err) {
+	g.work = g.bound = 0;
+	for (size_t i = 0; i < g.descs.size(); ++i) {
+		dgip::IpDesc& d = g.descs[i];
+		if (d.ref_len >= (1ull << 32) || d.delta_cap >= (1ull << 32))
+			return fail(err, DG_ERR_TOO_LARGE, "in-place plan: a stream of 4 GiB or more does not fit the u32 format");
+		d.work_off = g.work;
+		g.work += dgip::work_bytes(d.max_copies, d.max_adds);
+		g.bound += d.delta_cap + extra[i];
+	}
+	return DG_OK;
+}
+
+// descs with a_cap, b_cap, max_a and max_b filled
+int compose_finish(ComposeGeometry& g, std::string& err) {
+	g.work = 0;
+	for (dgcp::CpDesc& d : g.descs) {
+		if (d.a_cap >= (1ull << 32) || d.b_cap >= (1ull << 32))
+			return fail(err, DG_ERR_TOO_LARGE, "compose plan: a stream of 4 GiB or more does not fit the u32 format");
+		d.work_off = g.work;
+		g.work += dgcp::work_bytes(d.max_a, d.max_b);
+	}
+	return DG_OK;
+}
+
+// pair i's worst-case delta size and command count in an encode plan
+void compose_enc_pair(const EncodePlanView& e, uint32_t i, uint64_t* cap, uint32_t* cmds) {
+	*cap = pair_out_bound(e.algo, e.p, e.pairs[i].v_len);
+	// the encoders alternate COPY and ADD: at most one ADD before each COPY and one at the end
+	*cmds = (uint32_t)std::min<uint64_t>(2ull * e.pp[i].rec_cap + 1, compose_max_cmds(*cap));
+}
+
+}  // namespace
+
+int inplace_plan_geometry(const dg_inplace_desc_t* descs, uint32_t n, InplaceGeometry& g, std::string& err) {
+	g.descs.resize(n);
+	std::vector<uint64_t> extra(n);
+	for (uint32_t i = 0; i < n; ++i) {
+		const uint64_t cap = descs[i].delta_cap;
+		// 25 header bytes, then 13 per COPY and at least 9 per ADD
+		// (the END byte may be missing: encoding.c:111-178 stops at the stream's end too)
+		const uint64_t body = cap > 25 ? cap - 25 : 0;
+		g.descs[i] = dgip::IpDesc{descs[i].ref_off, descs[i].ref_len, descs[i].delta_off, cap, 0,
+		                          (uint32_t)std::min<uint64_t>(body / 13, 0xFFFFFFFFull),
+		                          (uint32_t)std::min<uint64_t>(body / 9, 0xFFFFFFFFull)};
+		extra[i] = std::min<uint64_t>((body / 13) * descs[i].ref_len, 1ull << 32);
+	}
+	return inplace_finish(extra, g, err);
+}
+
+int inplace_plan_geometry_for(const EncodePlanView& e, uint32_t n, InplaceGeometry& g, std::string& err) {
+	g.descs.resize(n);
+	std::vector<uint64_t> extra(n);
+	for (uint32_t i = 0; i < n; ++i) {
+		// the encoders alternate COPY and ADD: at most one ADD before each COPY and one at the end
+		g.descs[i] = dgip::IpDesc{e.pairs[i].r_off, e.pairs[i].r_len, 0, pair_out_bound(e.algo, e.p, e.pairs[i].v_len), 0,
+		                          e.pp[i].rec_cap, e.pp[i].rec_cap + 1};
+		extra[i] = e.pairs[i].v_len;
+	}
+	return inplace_finish(extra, g, err);
+}
+
+uint32_t compose_max_cmds(uint64_t cap) { return (uint32_t)std::min<uint64_t>(cap > 25 ? (cap - 25) / 9 : 0, 0xFFFFFFFEull); }
+
+int compose_plan_geometry(const dg_compose_desc_t* descs, uint32_t n, ComposeGeometry& g, std::string& err) {
+	g.descs.resize(n);
+	for (uint32_t i = 0; i < n; ++i)
+		g.descs[i] = dgcp::CpDesc{descs[i].a_off, descs[i].a_cap, descs[i].b_off, descs[i].b_cap, 0,
+		                          compose_max_cmds(descs[i].a_cap), compose_max_cmds(descs[i].b_cap)};
+	return compose_finish(g, err);
+}
+
+int compose_plan_geometry_for(const EncodePlanView& a, const EncodePlanView& b, uint32_t n, ComposeGeometry& g,
+                              std::string& err) {
+	g.descs.resize(n);
+	for (uint32_t i = 0; i < n; ++i) {
+		g.descs[i] = dgcp::CpDesc{};
+		compose_enc_pair(a, i, &g.descs[i].a_cap, &g.descs[i].max_a);
+		compose_enc_pair(b, i, &g.descs[i].b_cap, &g.descs[i].max_b);
+	}
+	return compose_finish(g, err);
 }
 
 // ── update plan: descriptor checks ──

@@ -9,6 +9,8 @@
 #include <vector>
 
 #include "../../include/delta_gpu.h"
+#include "dg_compose_dev.h"
+#include "dg_inplace_dev.h"
 #include "dg_layout.h"
 
 namespace dg {
@@ -87,6 +89,43 @@ struct EncodeGeometry {
 // Returns DG_OK, or the status with its message in err.
 int encode_geometry(dg_algorithm_t algo, const dg_diff_options_t& o, const dg_pair_t* pairs, uint32_t n,
                     const PlanEnv& env, EncodeGeometry& g, std::string& err);
+
+// The most bytes an encoder writes for a version of v_len bytes with seed
+// length p (>= 1): what an encode plan reserves per pair, and what a plan that
+// reads an encoder's deltas takes as their capacity.
+uint64_t pair_out_bound(dg_algorithm_t algo, uint64_t p, uint64_t v_len);
+
+// ── the transform plans' sizing (dg_inplace_host.cpp, dg_compose_host.cpp) ──
+// Each returns DG_OK with the device descriptors (work offsets assigned, 16-byte
+// aligned regions of work_bytes(...) each) and the work memory's size, or
+// DG_ERR_TOO_LARGE (a stream or reference of 4 GiB or more) with its message
+// in err.  The _for variants size from encode plans.
+
+// what they read of an encode plan of n pairs
+struct EncodePlanView {
+	const dg_pair_t* pairs;
+	const PairPlanDev* pp;
+	dg_algorithm_t algo;
+	uint64_t p;
+};
+
+struct InplaceGeometry {
+	std::vector<dgip::IpDesc> descs;
+	uint64_t work = 0;    // bytes of work memory
+	uint64_t bound = 0;   // dg_inplace_plan_output_bound: sum of capacity + the bytes COPYs can turn into ADD payload
+};
+int inplace_plan_geometry(const dg_inplace_desc_t* descs, uint32_t n, InplaceGeometry& g, std::string& err);
+int inplace_plan_geometry_for(const EncodePlanView& e, uint32_t n, InplaceGeometry& g, std::string& err);
+
+struct ComposeGeometry {
+	std::vector<dgcp::CpDesc> descs;
+	uint64_t work = 0;
+};
+// the most commands a stream of cap bytes holds (the END byte may be missing)
+uint32_t compose_max_cmds(uint64_t cap);
+int compose_plan_geometry(const dg_compose_desc_t* descs, uint32_t n, ComposeGeometry& g, std::string& err);
+int compose_plan_geometry_for(const EncodePlanView& a, const EncodePlanView& b, uint32_t n, ComposeGeometry& g,
+                              std::string& err);
 
 // dg_update_plan_create's descriptor checks: DG_OK, DG_ERR_TOO_LARGE (a buffer
 // or a length of 4 GiB or more) or DG_ERR_INVALID_ARG (a region wrapping the

@@ -15,6 +15,7 @@ import random
 import pytest
 
 import compose_cases as cc
+from stage_timing import check_ring_phases
 
 pytestmark = pytest.mark.gpu
 
@@ -271,6 +272,9 @@ def test_stage_times(dg, ctx, orc, torch_cuda):
     t = r.plan.stage_times()
     assert list(t) == ["map", "scan", "emit", "total"]
     assert all(v > 0 for v in t.values()) and t["total"] >= max(t["map"], t["scan"], t["emit"])
+    first = r.bytes
+    check_ring_phases(r.plan, lambda: r.run(out_cap=r.out_cap), ["map", "scan", "emit", "total"])
+    assert r.bytes == first
 
 
 def test_empty_plan_and_limits(dg, ctx, torch_cuda):

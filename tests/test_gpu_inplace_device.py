@@ -16,6 +16,7 @@ import random
 import pytest
 
 from inplace_graphs import POLICIES, build, named_graphs
+from stage_timing import check_ring_phases
 from test_oracle import inplace_inputs
 
 pytestmark = pytest.mark.gpu
@@ -35,9 +36,10 @@ def _arena(torch, chunks, size):
     return torch.frombuffer(buf, dtype=torch.uint8).cuda()
 
 
-def _run(torch, dg, ctx, items, policy, *, caps=None, out_cap=None, odd=False, timing=False):
+def _run(torch, dg, ctx, items, policy, *, caps=None, out_cap=None, odd=False, timing=False, after=None):
     """items: (R, stream) per delta -> (status list, outputs, offsets, plan).  odd:
-    streams and references at odd offsets, the last of each ending its arena."""
+    streams and references at odd offsets, the last of each ending its arena.
+    after(plan, go): called after the first run; go() runs the plan once more."""
     n = len(items)
     descs, rch, dch = [], [], []
     rt = dt = 1 if odd else 0
@@ -60,9 +62,14 @@ def _run(torch, dg, ctx, items, policy, *, caps=None, out_cap=None, odd=False, t
     off = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
     st = torch.full((n,), -1, dtype=torch.int32, device="cuda")
     torch.cuda.synchronize()
-    plan.run(ref_t.data_ptr(), del_t.data_ptr(), out.data_ptr(), cap_total, off.data_ptr(), st.data_ptr(),
-             stream=ctx.stream)
-    torch.cuda.synchronize()
+
+    def go():
+        plan.run(ref_t.data_ptr(), del_t.data_ptr(), out.data_ptr(), cap_total, off.data_ptr(), st.data_ptr(),
+                 stream=ctx.stream)
+        torch.cuda.synchronize()
+    go()
+    if after:
+        after(plan, go)
     offs = off.cpu().tolist()
     outc = bytes(out.cpu().numpy())
     return st.cpu().tolist(), [outc[offs[i]:offs[i + 1]] for i in range(n)], offs, plan
@@ -325,7 +332,11 @@ def test_streams_across_parse_windows(dg, ctx, orc, torch_cuda):
 # 8. stage timing
 def test_stage_times(dg, ctx, orc, torch_cuda):
     items = _random_items(dg, orc, 3, 16)
-    _, _, _, plan = _run(torch_cuda, dg, ctx, items, "localmin", timing=True)
-    t = plan.stage_times()
-    assert set(t) == {"order", "scan", "emit", "total"}
-    assert t["order"] > 0 and t["emit"] > 0 and t["total"] >= t["order"]
+    def first_then_phases(plan, go):
+        t = plan.stage_times()
+        assert set(t) == {"order", "scan", "emit", "total"}
+        assert t["order"] > 0 and t["emit"] > 0 and t["total"] >= t["order"]
+        check_ring_phases(plan, go, ["order", "scan", "emit", "total"])
+    st, outs, _, _ = _run(torch_cuda, dg, ctx, items, "localmin", timing=True, after=first_then_phases)
+    assert st == [OK] * len(items)
+    assert outs == [dg.make_inplace(R, d, "localmin") for R, d in items]

@@ -19,6 +19,7 @@ import random
 
 import pytest
 
+from stage_timing import check_ring_phases
 from test_oracle import inplace_inputs
 from update_cases import (DAMAGES, DECODE_AGREES, MOVE_KINDS, ORDER_KINDS, WINDOW, damage, make_delta, moves_case,
                           order_case, pad_noops, three_window_stream, version_size)
@@ -353,6 +354,11 @@ def test_plan_errors_and_surfaces(dg, ctx, orc, torch_cuda, base3):
     r = Run(torch_cuda, dg, ctx, [(R, d)], timing=True).run()
     t = r.plan.stage_times()
     assert set(t) >= {"update", "total"} and t["update"] > 0 and t["total"] >= t["update"]
+
+    def rerun():   # the buffer holds R again
+        r.load([(R, d)])
+        r.run().check_ok(0, V)
+    check_ring_phases(r.plan, rerun, ["update", "total"])
     # a mixed batch with one failing item: the host entry point equals the plan
     bad, _, want = damage(d, R, "cut_window3")
     items = [good[0][:2], (R, bad), (R, d), good[1][:2]]
