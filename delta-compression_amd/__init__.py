@@ -16,6 +16,9 @@ Names and argument meanings follow the reference's interface for this path:
 * ``compose(A, B)`` / ``ComposePlan`` / ``compose_batch`` — delta(R -> V1) and
   delta(V1 -> V2) joined into delta(R -> V2) without R, V1 or V2 (no reference
   counterpart; the normal form is stated in ``include/delta_gpu.h``).
+* ``invert(R, A)`` / ``InvertPlan`` / ``invert_batch`` — R and delta(R -> V)
+  turned into delta(V -> R) without V (no reference counterpart; the normal
+  form is stated in ``include/delta_gpu.h``).
 * ``info(delta)``                   — ``delta info`` (main.c:402-425).
 * ``diff`` / ``diff_greedy`` / ``diff_onepass`` / ``diff_correcting``, ``place_commands``,
   ``unplace_commands``, ``encode_delta``, ``decode_delta`` — the command-list
@@ -49,6 +52,8 @@ from ._lib import (  # noqa: F401
     UpdatePlan,
     ComposeDesc,
     ComposePlan,
+    InvertDesc,
+    InvertPlan,
     LIB_PATH,
     LIMIT_ONEPASS_MEMBERS,
     LIMIT_TABLE_POOL_BYTES,
@@ -75,6 +80,8 @@ from ._lib import (  # noqa: F401
     update_batch,
     compose,
     compose_batch,
+    invert,
+    invert_batch,
     output_size,
     place_commands,
     status_string,
@@ -85,6 +92,7 @@ __all__ = [
     "ALGO_ONEPASS", "ALGO_CORRECTING", "ALGO_GREEDY", "SEED_LEN", "TABLE_SIZE",
     "MAX_TABLE_SIZE", "BUF_CAP", "Context", "DeltaError", "DiffOptions", "EncodePlan", "DecodePlan", "InplacePlan", "UpdatePlan",
     "ComposeDesc", "ComposePlan", "compose", "compose_batch",
+    "InvertDesc", "InvertPlan", "invert", "invert_batch",
     "crc64_xz", "decode", "default_context", "encode", "encode_batch", "encode_pipelined", "info", "lib",
     "make_inplace", "make_inplace_batch", "update_batch", "status_string", "LIB_PATH", "LIMIT_TABLE_POOL_BYTES",
     "LIMIT_ONEPASS_MEMBERS", "MEMBERS_AUTO", "MEMBERS_ON", "MEMBERS_OFF",

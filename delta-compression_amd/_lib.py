@@ -88,6 +88,11 @@ class ComposeDesc(C.Structure):   # dg_compose_desc_t
     _fields_ = [("a_off", C.c_uint64), ("a_cap", C.c_uint64), ("b_off", C.c_uint64), ("b_cap", C.c_uint64)]
 
 
+class InvertDesc(C.Structure):   # dg_invert_desc_t
+    _fields_ = [("ref_off", C.c_uint64), ("ref_len", C.c_uint64),
+                ("delta_off", C.c_uint64), ("delta_cap", C.c_uint64)]
+
+
 class InplaceStats(C.Structure):
     _fields_ = [("already_inplace", C.c_int), ("num_copies", C.c_uint64), ("num_adds", C.c_uint64),
                 ("copy_bytes", C.c_uint64), ("add_bytes", C.c_uint64)]
@@ -209,6 +214,16 @@ def _load() -> C.CDLL:
         "dg_compose_plan_destroy": (None, [vp]),
         "dg_compose_batch": (C.c_int, [vp, C.POINTER(u8p), C.POINTER(sz), C.POINTER(u8p), C.POINTER(sz), u32,
                                        C.c_int, C.POINTER(Buffer), C.POINTER(i32)]),
+        "dg_invert": (C.c_int, [u8p, sz, u8p, sz, C.POINTER(Buffer)]),
+        "dg_invert_plan_create": (C.c_int, [vp, C.POINTER(InvertDesc), u32, C.POINTER(vp)]),
+        "dg_invert_plan_create_for": (C.c_int, [vp, vp, C.POINTER(vp)]),
+        "dg_invert_plan_output_bound": (u64, [vp]),
+        "dg_invert_plan_run": (C.c_int, [vp, vp, vp, vp, vp, vp, u64, vp, vp, vp]),
+        "dg_invert_plan_set_timing": (C.c_int, [vp, C.c_int]),
+        "dg_invert_plan_stage_times": (C.c_int, [vp, C.POINTER(C.c_float), C.POINTER(C.c_char_p), C.c_int]),
+        "dg_invert_plan_destroy": (None, [vp]),
+        "dg_invert_batch": (C.c_int, [vp, C.POINTER(u8p), C.POINTER(sz), C.POINTER(u8p), C.POINTER(sz), u32,
+                                      C.POINTER(Buffer), C.POINTER(i32)]),
         "dg_synth_edit_pairs_device": (C.c_int, [vp, vp, vp, u32, u64, u64, u64, vp]),
         "dg_synth_shift_pairs_device": (C.c_int, [vp, u64, u32, u64, u64, u32, C.POINTER(Pair),
                                                   C.POINTER(u64), C.POINTER(u64), vp, vp, vp]),
@@ -518,6 +533,40 @@ class ComposePlan(_Plan):
                                                d_out_offsets, d_status, stream or None), "dg_compose_plan_run")
 
 
+class InvertPlan(_Plan):
+    """dg_invert_plan_t: a batch of standard deltas inverted on the device, R
+    and delta(R -> V) giving delta(V -> R).  descs: (ref_off, ref_len,
+    delta_off, delta_cap) per delta, or for_plan: an EncodePlan whose packed
+    output the run inverts (pass its offsets and status to run)."""
+
+    _prefix = "dg_invert_plan"
+
+    def __init__(self, ctx: Context, descs: Optional[Sequence[Tuple[int, int, int, int]]] = None,
+                 for_plan: Optional["EncodePlan"] = None):
+        self.ctx = ctx
+        h = C.c_void_p()
+        if for_plan is not None:
+            ctx.check(lib.dg_invert_plan_create_for(ctx.handle, for_plan.handle, C.byref(h)),
+                      "dg_invert_plan_create_for")
+            self.n = for_plan.n
+        else:
+            n = len(descs)
+            arr = (InvertDesc * max(n, 1))(*[InvertDesc(*d) for d in descs])
+            ctx.check(lib.dg_invert_plan_create(ctx.handle, arr, n, C.byref(h)), "dg_invert_plan_create")
+            self.n = n
+        self.handle = h
+
+    @property
+    def output_bound(self) -> int:
+        return lib.dg_invert_plan_output_bound(self.handle)
+
+    def run(self, d_ref: int, d_delta: int, d_out: int, out_cap: int, d_out_offsets: int, d_status: int,
+            d_delta_offsets: int = 0, d_delta_status: int = 0, stream: int = 0):
+        self.ctx.check(lib.dg_invert_plan_run(self.handle, d_ref, d_delta, d_delta_offsets or None,
+                                              d_delta_status or None, d_out, out_cap, d_out_offsets, d_status,
+                                              stream or None), "dg_invert_plan_run")
+
+
 def encode(R: bytes, V: bytes, algorithm="onepass", p: int = SEED_LEN, q: int = TABLE_SIZE,
            buf_cap: int = BUF_CAP, max_table: int = MAX_TABLE_SIZE, splay: bool = False,
            inplace: bool = False, policy: str = "localmin",
@@ -705,6 +754,47 @@ def compose_batch(items: Sequence[Tuple[bytes, bytes]], ignore_hash: bool = Fals
     for i in range(n):
         if st[i]:
             raise DeltaError(st[i], f"pair {i}")
+    return res
+
+
+def invert(R: bytes, A: bytes) -> bytes:
+    """R and A = delta(R -> V) -> delta(V -> R) in normal form (dg_invert):
+    host only, and V is not needed."""
+    out = Buffer()
+    rc = lib.dg_invert(_u8(R), len(R), _u8(A), len(A), C.byref(out))
+    if rc:
+        raise DeltaError(rc, "dg_invert")
+    res = C.string_at(out.data, out.len) if out.len else b""
+    lib.dg_buffer_free(C.byref(out))
+    return res
+
+
+def invert_batch(items: Sequence[Tuple[bytes, bytes]], ctx: Optional[Context] = None, status: bool = False):
+    """(R, delta(R -> V)) pairs inverted on the device in one batch
+    (dg_invert_batch); equal to invert item by item.  Raises DeltaError for
+    the first failing item; with status=True returns (results, statuses)
+    instead, a failed item's result being b""."""
+    ctx = ctx or default_context()
+    n = len(items)
+    if n == 0:
+        return ([], []) if status else []
+    keep = [(bytes(r), bytes(d)) for r, d in items]
+    rp = (C.POINTER(C.c_uint8) * n)(*[_u8(r) for r, _ in keep])
+    dp = (C.POINTER(C.c_uint8) * n)(*[_u8(d) for _, d in keep])
+    rl = (C.c_size_t * n)(*[len(r) for r, _ in keep])
+    dl = (C.c_size_t * n)(*[len(d) for _, d in keep])
+    outs = (Buffer * n)()
+    st = (C.c_int32 * n)()
+    ctx.check(lib.dg_invert_batch(ctx.handle, rp, rl, dp, dl, n, outs, st), "dg_invert_batch")
+    res = []
+    for i in range(n):
+        res.append(C.string_at(outs[i].data, outs[i].len) if outs[i].len else b"")
+        lib.dg_buffer_free(C.byref(outs[i]))
+    if status:
+        return res, list(st)
+    for i in range(n):
+        if st[i]:
+            raise DeltaError(st[i], f"delta {i}")
     return res
 
 

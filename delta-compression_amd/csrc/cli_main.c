@@ -11,13 +11,16 @@
  *   delta info <delta>
  *   delta inplace <ref> <delta_in> <delta_out> [--policy localmin|constant]
  *   delta compose <delta_ab> <delta_bc> <delta_out> [--ignore-hash]
+ *   delta invert <ref> <delta_in> <delta_out> [--ignore-hash]
  *
  * --inplace / inplace run the CRWI conversion on the host (dg_make_inplace,
  * main.c:279-283 and :427-480).  --splay applies to greedy only (its tie-break
  * among the longest matches); with onepass or correcting it is not provided
  * by this build (exit 1 with a message).  compose joins delta(R -> V1) and
  * delta(V1 -> V2) into delta(R -> V2) on the host (dg_compose): no GPU and
- * none of R, V1 or V2.
+ * none of R, V1 or V2.  invert turns R and delta(R -> V) into delta(V -> R) on
+ * the host (dg_invert) without V; it first checks R's CRC against the delta's
+ * (on the GPU, as decode does) unless --ignore-hash is given.
  */
 #include <errno.h>
 #include <getopt.h>
@@ -93,6 +96,7 @@ static void usage(void)
 	    "  delta info <delta>\n"
 	    "  delta inplace <ref> <delta_in> <delta_out> [--policy P]\n"
 	    "  delta compose <delta_ab> <delta_bc> <delta_out> [--ignore-hash]\n"
+	    "  delta invert <ref> <delta_in> <delta_out> [--ignore-hash]\n"
 	    "\n"
 	    "Algorithms: greedy, onepass, correcting (MI355X)\n"
 	    "\n"
@@ -399,6 +403,69 @@ static int cmd_compose(int argc, char **argv)
 	return 0;
 }
 
+static int cmd_invert(int argc, char **argv)
+{
+	if (argc < 5) usage();
+	const char *ref_path = argv[2], *in_path = argv[3], *out_path = argv[4];
+	int ignore = 0;
+	for (int k = 5; k < argc; k++)
+		if (strcmp(argv[k], "--ignore-hash") == 0) ignore = 1;
+	size_t rl, dl;
+	uint8_t *r = read_file(ref_path, &rl), *d = read_file(in_path, &dl);
+	if (!is_delta_file(d, dl)) {
+		fprintf(stderr, "delta_invert: not a delta file\n");
+		return 1;
+	}
+	if (!ignore) {
+		/* the library does not check R: the inverse would only fail when decoded */
+		dg_context_t *ctx = ctx_or_die();
+		uint8_t c[8];
+		int rc = dg_crc64_xz(ctx, r, rl, c);
+		dg_context_destroy(ctx);
+		if (rc) {
+			fprintf(stderr, "delta_invert: %s\n", dg_status_string(rc));
+			return 1;
+		}
+		if (memcmp(c, d + 9, 8) != 0) {
+			fprintf(stderr, "source file does not match delta: expected ");
+			hex(stderr, d + 9, 8);
+			fprintf(stderr, ", got ");
+			hex(stderr, c, 8);
+			fprintf(stderr, "\n");
+			return 1;
+		}
+	}
+	dg_buffer_t o = {0};
+	double t0 = now();
+	int rc = dg_invert(r, rl, d, dl, &o);
+	double t1 = now();
+	if (rc == DG_ERR_UNSUPPORTED) {
+		fprintf(stderr, "delta_invert: unsupported input (an in-place delta, or commands not placed in sequence)\n");
+		return 1;
+	}
+	if (rc) {
+		fprintf(stderr, "delta_invert: %s\n", dg_status_string(rc));
+		return 1;
+	}
+	write_file(out_path, o.data, o.len);
+	dg_delta_info_t inf;
+	dg_delta_info(o.data, o.len, &inf);
+	printf("Reference:    %s (%zu bytes)\n", ref_path, rl);
+	printf("Input delta:  %s (%zu bytes)\n", in_path, dl);
+	printf("Output delta: %s (%zu bytes)\n", out_path, o.len);
+	printf("Commands:     %llu copies, %llu adds\n", (unsigned long long)inf.num_copies,
+	       (unsigned long long)inf.num_adds);
+	printf("Copy bytes:   %llu\n", (unsigned long long)inf.copy_bytes);
+	printf("Add bytes:    %llu\n", (unsigned long long)inf.add_bytes);
+	printf("Src CRC:      "); hex(stdout, inf.src_crc, 8); printf("\n");
+	printf("Dst CRC:      "); hex(stdout, inf.dst_crc, 8); printf("\n");
+	printf("Time:         %.3fs\n", t1 - t0);
+	dg_buffer_free(&o);
+	free(r);
+	free(d);
+	return 0;
+}
+
 int main(int argc, char **argv)
 {
 	if (argc < 2) usage();
@@ -407,6 +474,7 @@ int main(int argc, char **argv)
 	if (strcmp(argv[1], "info") == 0) return cmd_info(argc, argv);
 	if (strcmp(argv[1], "inplace") == 0) return cmd_inplace(argc, argv);
 	if (strcmp(argv[1], "compose") == 0) return cmd_compose(argc, argv);
+	if (strcmp(argv[1], "invert") == 0) return cmd_invert(argc, argv);
 	usage();
 	return 1;
 }

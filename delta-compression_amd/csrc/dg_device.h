@@ -189,13 +189,13 @@ uint64_t ctx_limits_gen(const dg_context_t* ctx);   // changes with every dg_con
 int ctx_device(const dg_context_t* ctx);            // the context's HIP device
 // the plan's per-pair parameters (n_pairs records; for print_verbose, dg_plan.h)
 const PairPlanDev* plan_pp(const dg_encode_plan_t* P);
-// what dg_inplace_plan_create_for and dg_compose_plan_create_for read of an encode plan
+// what dg_inplace_plan_create_for, dg_compose_plan_create_for and dg_invert_plan_create_for read of an encode plan
 const dg_pair_t* plan_pairs(const dg_encode_plan_t* P);
 dg_context_t* plan_ctx(const dg_encode_plan_t* P);
 void plan_options(const dg_encode_plan_t* P, dg_algorithm_t* algo, dg_diff_options_t* opts);
 // the context's slots for code objects loaded at run time, one per module
 // (filled by load_kernels, dg_hostutil.h)
-enum : int { kCtxModInplace = 0, kCtxModUpdate = 1, kCtxModCompose = 2, kCtxModules = 3 };
+enum : int { kCtxModInplace = 0, kCtxModUpdate = 1, kCtxModCompose = 2, kCtxModInvert = 3, kCtxModules = 4 };
 void** ctx_module(dg_context_t* ctx, int slot, void (*release)(void*));
 const uint64_t* ctx_crc_tables(const dg_context_t* ctx);     // the CRC tables on the device (CrcArgs::tables)
 int ctx_fail(dg_context_t* ctx, int code, const char* msg);   // records dg_last_error, returns code

@@ -46,7 +46,8 @@ struct dg_context {
 	void (*io_free)(void*) = nullptr;
 	// code objects loaded at run time: the in-place conversion module
 	// (dg_inplace_host.cpp), the in-place update module (dg_update_host.cpp),
-	// the composition module (dg_compose_host.cpp)
+	// the composition module (dg_compose_host.cpp), the inversion module
+	// (dg_invert_host.cpp)
 	void* module[kCtxModules] = {};
 	void (*module_free[kCtxModules])(void*) = {};
 };

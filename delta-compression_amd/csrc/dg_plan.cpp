@@ -555,7 +555,7 @@ void print_verbose(dg_algorithm_t algo, const dg_diff_options_t& o, const dg_pai
 	print_command_stats(cmds);
 }
 
-// ── in-place and compose plans: descriptors, work memory, bounds ──
+// ── in-place, compose and invert plans: descriptors, work memory, bounds ──
 
 namespace {
 
@@ -591,6 +591,19 @@ void compose_enc_pair(const EncodePlanView& e, uint32_t i, uint64_t* cap, uint32
 	*cap = pair_out_bound(e.algo, e.p, e.pairs[i].v_len);
 	// the encoders alternate COPY and ADD: at most one ADD before each COPY and one at the end
 	*cmds = (uint32_t)std::min<uint64_t>(2ull * e.pp[i].rec_cap + 1, compose_max_cmds(*cap));
+}
+
+// descs with ref_len, delta_cap and max_copies filled
+int invert_finish(InvertGeometry& g, std::string& err) {
+	g.work = g.bound = 0;
+	for (dgiv::IvDesc& d : g.descs) {
+		if (d.ref_len >= (1ull << 32) || d.delta_cap >= (1ull << 32))
+			return fail(err, DG_ERR_TOO_LARGE, "invert plan: a stream or reference of 4 GiB or more does not fit the u32 format");
+		d.work_off = g.work;
+		g.work += dgiv::work_bytes(d.max_copies);
+		g.bound += dgiv::out_bound(d.max_copies, d.ref_len);
+	}
+	return DG_OK;
 }
 
 }  // namespace
@@ -642,6 +655,27 @@ int compose_plan_geometry_for(const EncodePlanView& a, const EncodePlanView& b, 
 		compose_enc_pair(b, i, &g.descs[i].b_cap, &g.descs[i].max_b);
 	}
 	return compose_finish(g, err);
+}
+
+// 25 header bytes, 13 per COPY and the END byte
+uint32_t invert_max_copies(uint64_t cap) { return (uint32_t)std::min<uint64_t>(cap > 26 ? (cap - 26) / 13 : 0, 0xFFFFFFFEull); }
+
+int invert_plan_geometry(const dg_invert_desc_t* descs, uint32_t n, InvertGeometry& g, std::string& err) {
+	g.descs.resize(n);
+	for (uint32_t i = 0; i < n; ++i)
+		g.descs[i] = dgiv::IvDesc{descs[i].ref_off, descs[i].ref_len, descs[i].delta_off, descs[i].delta_cap, 0,
+		                          invert_max_copies(descs[i].delta_cap), 0};
+	return invert_finish(g, err);
+}
+
+int invert_plan_geometry_for(const EncodePlanView& e, uint32_t n, InvertGeometry& g, std::string& err) {
+	g.descs.resize(n);
+	for (uint32_t i = 0; i < n; ++i) {
+		const uint64_t cap = pair_out_bound(e.algo, e.p, e.pairs[i].v_len);
+		g.descs[i] = dgiv::IvDesc{e.pairs[i].r_off, e.pairs[i].r_len, 0, cap, 0,
+		                          std::min<uint32_t>(e.pp[i].rec_cap, invert_max_copies(cap)), 0};
+	}
+	return invert_finish(g, err);
 }
 
 // ── update plan: descriptor checks ──

@@ -11,6 +11,7 @@
 #include "../../include/delta_gpu.h"
 #include "dg_compose_dev.h"
 #include "dg_inplace_dev.h"
+#include "dg_invert_dev.h"
 #include "dg_layout.h"
 
 namespace dg {
@@ -95,7 +96,7 @@ int encode_geometry(dg_algorithm_t algo, const dg_diff_options_t& o, const dg_pa
 // reads an encoder's deltas takes as their capacity.
 uint64_t pair_out_bound(dg_algorithm_t algo, uint64_t p, uint64_t v_len);
 
-// ── the transform plans' sizing (dg_inplace_host.cpp, dg_compose_host.cpp) ──
+// ── the transform plans' sizing (dg_inplace_host.cpp, dg_compose_host.cpp, dg_invert_host.cpp) ──
 // Each returns DG_OK with the device descriptors (work offsets assigned, 16-byte
 // aligned regions of work_bytes(...) each) and the work memory's size, or
 // DG_ERR_TOO_LARGE (a stream or reference of 4 GiB or more) with its message
@@ -126,6 +127,16 @@ uint32_t compose_max_cmds(uint64_t cap);
 int compose_plan_geometry(const dg_compose_desc_t* descs, uint32_t n, ComposeGeometry& g, std::string& err);
 int compose_plan_geometry_for(const EncodePlanView& a, const EncodePlanView& b, uint32_t n, ComposeGeometry& g,
                               std::string& err);
+
+struct InvertGeometry {
+	std::vector<dgiv::IvDesc> descs;
+	uint64_t work = 0;
+	uint64_t bound = 0;   // dg_invert_plan_output_bound: sum of dgiv::out_bound
+};
+// the most COPYs a stream of cap bytes holds
+uint32_t invert_max_copies(uint64_t cap);
+int invert_plan_geometry(const dg_invert_desc_t* descs, uint32_t n, InvertGeometry& g, std::string& err);
+int invert_plan_geometry_for(const EncodePlanView& e, uint32_t n, InvertGeometry& g, std::string& err);
 
 // dg_update_plan_create's descriptor checks: DG_OK, DG_ERR_TOO_LARGE (a buffer
 // or a length of 4 GiB or more) or DG_ERR_INVALID_ARG (a region wrapping the

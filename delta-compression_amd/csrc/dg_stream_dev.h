@@ -1,5 +1,5 @@
 // dg_stream_dev.h — what the kernels that read and write whole delta streams
-// share (dg_inplace_dev.hip, dg_compose_dev.hip): big-endian fields, the
+// share (dg_inplace_dev.hip, dg_compose_dev.hip, dg_invert_dev.hip): big-endian fields, the
 // lane-owned command header of the parser's window (dg_parse_chain.h), a 64-bit
 // wave scan and the emit kernels' wave copy.  Device code only.
 #pragma once

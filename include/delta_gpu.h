@@ -772,6 +772,132 @@ int dg_compose_batch(dg_context_t *ctx, const uint8_t *const *a, const size_t *a
                      const uint8_t *const *b, const size_t *b_len, uint32_t n,
                      int ignore_hash, dg_buffer_t *outs, int32_t *status);
 
+/* ── inversion: R and delta(R -> V) give delta(V -> R) ────────────────────────
+ *
+ * A store that keeps the newest version whole and older ones as backward
+ * deltas encodes A = delta(R -> V) on a commit and then needs delta(V -> R) to
+ * drop R.  A already holds everything the inverse can hold: every byte of R
+ * that some COPY of A reads is in V at a known offset, and every other byte of
+ * R has to be carried as a literal.  So the inverse is a pure transform of A's
+ * command list plus the uncovered bytes of R: no V, no fingerprints, no
+ * tables.  (The reference has no such function.)  With dg_compose it closes
+ * the set: compose(invert(A), B) re-bases a chain without re-encoding.
+ *
+ * Inputs.  R of ref_len bytes, and A, a standard delta (header flag clear)
+ * against R: a sequentially placed exact cover, as for dg_compose.
+ *
+ * Provenance of R.  A COPY(src, dst, len) of A with len > 0 covers position x
+ * of R when src <= x < src + len.  If no COPY covers x, x is a literal with
+ * the byte R[x].  Otherwise x's owner is, among the covering COPYs, the one
+ * with the smallest src; among those the longest; among those the first in
+ * the stream; and x comes from V at owner.dst + (x - owner.src).
+ * Equivalently: sort the COPYs by (src ascending, len descending, stream
+ * index ascending) and sweep with a running maximum `reach` of the ends seen
+ * so far; COPY j owns [max(src_j, reach), src_j + len_j) when that interval is
+ * not empty, and the bytes between reach and a later src_j, and between the
+ * final reach and ref_len, are literals.  ADDs of A and zero-length commands
+ * contribute nothing.
+ *
+ * Normal form.  That map, run-length encoded over x = 0 .. ref_len - 1:
+ * consecutive literals are one ADD; consecutive V positions are one COPY
+ * whenever the V offset also advances by one, whichever owners they came from
+ * (two touching COPYs of A whose dst ranges also touch merge; a shadowed COPY
+ * vanishes).  No zero-length command is emitted, dst is sequential, the
+ * header is DLT\x03 with flag byte 0, version_size = ref_len, src_crc =
+ * A.dst_crc, dst_crc = A.src_crc, and one END byte closes the stream.  The
+ * host function, the device path and the tests' Python model produce it byte
+ * for byte; every decoder here and the reference's `delta decode` decode it
+ * against V to R with both CRC checks passing.
+ *
+ * Status, per delta.  The kind of defect decides, not its position in the
+ * stream; first match wins:
+ *   (incoming)          a nonzero d_delta_status[i] is passed on;
+ *   DG_ERR_MALFORMED    magic, framing, an unknown command, a payload past the
+ *                       end, or a COPY with src + len > ref_len;
+ *   DG_ERR_CAPACITY     (device) a stream longer than its capacity, or more
+ *                       COPYs than the plan's work memory holds;
+ *   DG_ERR_UNSUPPORTED  the in-place flag is set; placement is not sequential;
+ *                       the lengths do not sum to version_size;
+ *   DG_ERR_TOO_LARGE    the inverse would be 4 GiB or more;
+ *   DG_ERR_CAPACITY     (device) the delta's output ends past out_cap.
+ * A failed delta's output is empty and its neighbours are untouched; for a
+ * delta that fails on out_cap the offsets still count its size.
+ *
+ * R's CRC is not checked by the library: the inverse's dst_crc is A.src_crc,
+ * so a wrong R shows as DG_ERR_DST_CRC when the inverse is decoded.  (`delta
+ * invert` checks it unless --ignore-hash is given.)
+ *
+ * dg_invert is pure host code (no context, no GPU): linear in input plus
+ * output apart from one sort of the COPYs; *out is malloc'd.  An R or a
+ * stream of 4 GiB or more is DG_ERR_TOO_LARGE. */
+int dg_invert(const uint8_t *r, size_t r_len, const uint8_t *a, size_t a_len,
+              dg_buffer_t *out);
+
+/* ── inversion of a batch on the device ────────────────────────────────────
+ *
+ * The same transform, byte for byte, for N deltas: the references in one
+ * device arena, the streams in another (packed as the encode plan writes
+ * them, or one per descriptor), the inverses packed at
+ * d_out[d_out_offsets[i] .. d_out_offsets[i+1]), n + 1 offsets.  One wave per
+ * delta parses the stream, puts its COPYs into key order (skipped when the
+ * stream has them so already, as every encoder whose matches move forward in
+ * both buffers emits them; else a radix sort by that wave) and sweeps them;
+ * the size scan packs the outputs; one block per delta writes them.  A run is
+ * two kernels and the scan on one stream: no allocation, no host
+ * synchronisation, graph-capturable like its siblings.  So
+ * dg_encode_plan_run -> dg_invert_plan_run turn (R, V) into delta(V -> R) on
+ * one stream with no host step.
+ *
+ * Offsets.  With d_delta_offsets (n + 1 entries, as dg_encode_plan_run writes
+ * them) stream i is d_delta[d_delta_offsets[i] .. d_delta_offsets[i+1]) and
+ * delta_cap only bounds its length; with NULL it is exactly delta_cap bytes at
+ * delta_off.  The d_ref, d_delta and d_out ranges must not overlap.
+ *
+ * Sizing.  With C possible COPYs the inverse has at most 2 C + 1 runs, so one
+ * delta needs at most 25 + 13 C + 9 (C + 1) + ref_len + 1 bytes;
+ * dg_invert_plan_output_bound is the sum over the batch.
+ *
+ * Work memory is allocated at plan creation from the capacities: (delta_cap -
+ * 26) / 13 possible COPYs (a plan made from an encode plan uses the encoder's
+ * record capacity), 64 bytes per possible COPY; DG_ERR_NOMEM when it cannot be
+ * had.  A capacity or ref_len of 4 GiB or more is DG_ERR_TOO_LARGE; n == 0 is
+ * a valid empty plan.  One wave sorts and sweeps one delta's COPYs, so a delta
+ * with very many COPYs out of key order holds its wave for eight passes over
+ * them.
+ *
+ * The kernels live in dg_invert.hsaco beside libdeltagpu.so and are loaded on
+ * first use; DG_ERR_HIP with the path in dg_last_error when it is missing.
+ * Stage timing as for the in-place plan: "map", "scan", "emit", "total". */
+typedef struct {
+	uint64_t ref_off, ref_len;       /* R_i in d_ref */
+	uint64_t delta_off, delta_cap;   /* delta(R -> V) i: start, and most bytes it may have */
+} dg_invert_desc_t;
+typedef struct dg_invert_plan dg_invert_plan_t;
+
+int dg_invert_plan_create(dg_context_t *ctx, const dg_invert_desc_t *descs /* host */,
+                          uint32_t n, dg_invert_plan_t **out);
+/* Geometry from an encode plan: its R spans, worst-case delta sizes and record
+ * capacities; pass dg_encode_plan_run's offsets and statuses to the run. */
+int dg_invert_plan_create_for(dg_context_t *ctx, const dg_encode_plan_t *enc,
+                              dg_invert_plan_t **out);
+uint64_t dg_invert_plan_output_bound(const dg_invert_plan_t *plan);
+int dg_invert_plan_run(dg_invert_plan_t *plan, const uint8_t *d_ref,
+                       const uint8_t *d_delta, const uint64_t *d_delta_offsets,
+                       const int32_t *d_delta_status,
+                       uint8_t *d_out, uint64_t out_cap,
+                       uint64_t *d_out_offsets, int32_t *d_status, void *stream);
+int dg_invert_plan_set_timing(dg_invert_plan_t *plan, int slots);
+int dg_invert_plan_stage_times(dg_invert_plan_t *plan, float *ms,
+                               const char **names, int n);
+void dg_invert_plan_destroy(dg_invert_plan_t *plan);
+
+/* Host buffers in, host buffers out (outs[i] malloc'd, status may be NULL).
+ * Returns DG_OK (per-delta failures in status) or the first failure when
+ * status is NULL. */
+int dg_invert_batch(dg_context_t *ctx, const uint8_t *const *r, const size_t *r_len,
+                    const uint8_t *const *delta, const size_t *delta_len, uint32_t n,
+                    dg_buffer_t *outs, int32_t *status);
+
 /* ── synthetic batch generators (bench / test inputs, on the device) ─────
  * Workload definitions in DESIGN.md ("Synthetic inputs"); the oracle's
  * or_synth_* functions produce the same bytes on the CPU. */
