@@ -284,9 +284,17 @@ class Context:
         if rc:
             raise DeltaError(rc, "dg_context_create")
         self.handle = h
+        # live plan handles -> their destroy function.  A plan's destroy uses its
+        # context, and the collector finalises a context and its plans in any
+        # order once they are garbage together, so the context, closed first,
+        # destroys them (_Plan.close then finds nothing left to do)
+        self._plans = {}
 
     def close(self):
         if self.handle:
+            for h, destroy in list(self._plans.items()):
+                destroy(C.c_void_p(h))
+            self._plans.clear()
             lib.dg_context_destroy(self.handle)
             self.handle = None
 
@@ -337,9 +345,16 @@ class _Plan:
         k = getattr(lib, self._prefix + "_stage_times")(self.handle, ms, names, 8)
         return {names[i].decode(): ms[i] for i in range(k)}
 
+    def _own(self, h):
+        """Take the created handle; the context destroys it if it closes first."""
+        self.handle = h
+        self.ctx._plans[h.value] = getattr(lib, self._prefix + "_destroy")
+
     def close(self):
         if self.handle:
-            getattr(lib, self._prefix + "_destroy")(self.handle)
+            destroy = self.ctx._plans.pop(self.handle.value, None)
+            if destroy is not None:   # (None: the context closed before this plan and took it along)
+                destroy(self.handle)
             self.handle = None
 
     def __del__(self):
@@ -367,7 +382,7 @@ class EncodePlan(_Plan):
         h = C.c_void_p()
         ctx.check(lib.dg_encode_plan_create(ctx.handle, _algo(algorithm), arr, n, C.byref(o),
                                             C.byref(h)), "dg_encode_plan_create")
-        self.handle = h
+        self._own(h)
         self.n = n
 
     @property
@@ -427,7 +442,7 @@ class DecodePlan(_Plan):
         h = C.c_void_p()
         ctx.check(lib.dg_decode_plan_create(ctx.handle, arr, n, int(ignore_hash), C.byref(h)),
                   "dg_decode_plan_create")
-        self.handle = h
+        self._own(h)
         self.n = n
 
     def run(self, d_ref: int, d_delta: int, d_out: int, d_out_len: int, d_status: int,
@@ -463,7 +478,7 @@ class InplacePlan(_Plan):
             ctx.check(lib.dg_inplace_plan_create(ctx.handle, arr, n, POLICIES[policy], C.byref(h)),
                       "dg_inplace_plan_create")
             self.n = n
-        self.handle = h
+        self._own(h)
 
     @property
     def output_bound(self) -> int:
@@ -491,7 +506,7 @@ class UpdatePlan(_Plan):
         h = C.c_void_p()
         ctx.check(lib.dg_update_plan_create(ctx.handle, arr, n, int(ignore_hash), C.byref(h)),
                   "dg_update_plan_create")
-        self.handle = h
+        self._own(h)
         self.n = n
 
     def run(self, d_buf: int, d_delta: int, d_out_len: int, d_status: int, d_delta_offsets: int = 0,
@@ -524,7 +539,7 @@ class ComposePlan(_Plan):
             ctx.check(lib.dg_compose_plan_create(ctx.handle, arr, n, int(ignore_hash), C.byref(h)),
                       "dg_compose_plan_create")
             self.n = n
-        self.handle = h
+        self._own(h)
 
     def run(self, d_a: int, d_b: int, d_out: int, out_cap: int, d_out_offsets: int, d_status: int,
             d_a_offsets: int = 0, d_a_status: int = 0, d_b_offsets: int = 0, d_b_status: int = 0, stream: int = 0):
@@ -554,7 +569,7 @@ class InvertPlan(_Plan):
             arr = (InvertDesc * max(n, 1))(*[InvertDesc(*d) for d in descs])
             ctx.check(lib.dg_invert_plan_create(ctx.handle, arr, n, C.byref(h)), "dg_invert_plan_create")
             self.n = n
-        self.handle = h
+        self._own(h)
 
     @property
     def output_bound(self) -> int:

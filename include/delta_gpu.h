@@ -199,6 +199,24 @@ uint32_t dg_encode_plan_num_pairs(const dg_encode_plan_t *plan);
 /* Table size q actually used for pair i (onepass.c:61-62 /
  * correcting.c:116-123 sizing); 0 for a greedy plan, which has none. */
 uint64_t dg_encode_plan_table_size(const dg_encode_plan_t *plan, uint32_t i);
+/* One run of the plan over the bytes the arenas hold when the stream reaches
+ * it; a plan is run any number of times, on other bytes of the same layout
+ * each time, and no run sees anything of the runs before it.
+ *   Arguments.  d_ref_arena and d_ver_arena are 16-byte aligned; d_out needs
+ *     no alignment.  A NULL device pointer or a misaligned arena returns
+ *     DG_ERR_INVALID_ARG before anything is enqueued.  A plan of zero pairs
+ *     returns DG_OK and touches nothing (every pointer may be NULL).
+ *   Sizes.  d_offsets always receives the true sizes: d_offsets[i+1] -
+ *     d_offsets[i] is the size of pair i's delta whether or not it was
+ *     written, so d_offsets[N] is the out_cap with which every pair fits
+ *     (at most dg_encode_plan_output_bound).
+ *   Capacity.  A pair whose end d_offsets[i+1] passes out_cap gets
+ *     DG_ERR_CAPACITY and writes nothing, not even its header; the pairs
+ *     before it are complete.
+ *   Containment.  No byte outside d_out[0 .. min(d_offsets[N], out_cap)) is
+ *     written, and of d_offsets and d_status only entries [0, N] and [0, N).
+ *   Status.  Every run sets every d_status[i] anew: no status, size or other
+ *     state of an earlier run stays with the plan. */
 int dg_encode_plan_run(dg_encode_plan_t *plan,
                        const uint8_t *d_ref_arena, const uint8_t *d_ver_arena,
                        uint8_t *d_out, uint64_t out_cap,
