@@ -41,20 +41,6 @@ using namespace dgcp;
 
 namespace {
 
-// 1 + the nearest earlier lane whose flag is set, 0 when there is none
-__device__ __forceinline__ uint32_t prev_set(bool f, uint32_t lane) {
-	return wave_shr1z(wave_incl_max(f ? lane + 1u : 0u));
-}
-// 1 + the last lane whose flag is set, 0 when there is none (uniform)
-__device__ __forceinline__ uint32_t last_set(bool f) {
-	const uint64_t m = __ballot(f);
-	return m ? 64u - (uint32_t)__builtin_clzll(m) : 0u;
-}
-__device__ __forceinline__ uint32_t shfl32(uint32_t x, uint32_t l) { return (uint32_t)__shfl((int)x, (int)(l & 63u), 64); }
-__device__ __forceinline__ uint64_t shfl64(uint64_t x, uint32_t l) {
-	return ((uint64_t)shfl32((uint32_t)(x >> 32), l) << 32) | shfl32((uint32_t)x, l);
-}
-
 struct ATab {
 	uint32_t *v, *ref, *H, *HA, *AP;
 };
@@ -133,11 +119,11 @@ extern "C" __global__ __launch_bounds__(64) void dg_compose_map_kernel(CpArgs a)
 
 	// ── stream A: validate, fill the tables ──
 	uint32_t vsA = 0, nA = 0;
-	if (al < 25 || SA[0] != 'D' || SA[1] != 'L' || SA[2] != 'T' || SA[3] != 3) {
+	if (bad_magic(SA, al)) {
 		bad = true;
 	} else {
 		if (SA[4] & 1) unsup = true;
-		vsA = be32_at(SA + 5);
+		vsA = be32(SA + 5);
 		uint32_t pos = 25, heads = 0, aheads = 0;
 		uint64_t wpos = 0, addb = 0;
 		bool c_has = false, ended = false;   // the last non-empty command so far: its kind and where its COPY ends in R
@@ -145,7 +131,7 @@ extern "C" __global__ __launch_bounds__(64) void dg_compose_map_kernel(CpArgs a)
 		uint64_t c_end = 0;
 		while (!ended && !bad) {
 			if (pos >= al) break;   // the stream ends without an END byte
-			const ChainWindow cw = chain_window(SA, al, pos, cl);
+			const auto cw = chain_window<64>(cl, cl.win, chain_load_wave(cl.win, SA, al, pos), pos, al);
 			for (uint32_t b0 = 0; b0 < cw.cnt; b0 += 64) {
 				const bool mine = b0 + lane < cw.cnt;
 				const Hdr h = decode_hdr(win, cmds, b0 + lane, mine);
@@ -214,11 +200,11 @@ extern "C" __global__ __launch_bounds__(64) void dg_compose_map_kernel(CpArgs a)
 	bool huge = false;
 	bool o_has = false;   // the run open after the commands so far: its length field and where it starts in V2
 	uint32_t o_lf = 0, o_v = 0;
-	if (bl < 25 || SB[0] != 'D' || SB[1] != 'L' || SB[2] != 'T' || SB[3] != 3) {
+	if (bad_magic(SB, bl)) {
 		bad = true;
 	} else {
 		if (SB[4] & 1) unsup = true;
-		vsB = be32_at(SB + 5);
+		vsB = be32(SB + 5);
 		uint32_t pos = 25;
 		uint64_t wpos = 0;
 		bool c_has = false, ended = false;   // the last non-empty command so far: its last run's kind and end in R
@@ -226,7 +212,7 @@ extern "C" __global__ __launch_bounds__(64) void dg_compose_map_kernel(CpArgs a)
 		uint64_t c_rend = 0;
 		while (!ended && !bad) {
 			if (pos >= bl) break;
-			const ChainWindow cw = chain_window(SB, bl, pos, cl);
+			const auto cw = chain_window<64>(cl, cl.win, chain_load_wave(cl.win, SB, bl, pos), pos, bl);
 			for (uint32_t b0 = 0; b0 < cw.cnt; b0 += 64) {
 				const bool mine = b0 + lane < cw.cnt;
 				const Hdr h = decode_hdr(win, cmds, b0 + lane, mine);
@@ -383,12 +369,12 @@ extern "C" __global__ __launch_bounds__(256) void dg_compose_emit_kernel(CpArgs 
 			cmd = SB + r.pos;
 			kind = cmd[0];
 			if (kind == 1) {
-				s = be32_at(cmd + 1);
-				vcur = be32_at(cmd + 5);
-				len = be32_at(cmd + 9);
+				s = be32(cmd + 1);
+				vcur = be32(cmd + 5);
+				len = be32(cmd + 9);
 			} else {
-				vcur = be32_at(cmd + 1);
-				len = be32_at(cmd + 5);
+				vcur = be32(cmd + 1);
+				len = be32(cmd + 5);
 			}
 			x = s;
 			e = s + len;

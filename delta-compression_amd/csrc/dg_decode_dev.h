@@ -1,8 +1,9 @@
-// dg_decode_dev.h — the decode side's device functions: the four-wave window
-// parser's pieces, the flat and grouped apply, and the in-kernel CRC segment
-// helpers.  Shared by decode_kernel (dg_kernels.hip) and the in-place update
-// kernel (dg_update_dev.hip, the stand-alone code object lib/dg_update.hsaco);
-// moved here from dg_kernels.hip as they were.
+// dg_decode_dev.h — the decode side's device functions: the LDS layout of a
+// four-wave block, the window step (load, the command chain of
+// dg_parse_chain.h, the bounds and order checks), the flat and grouped apply,
+// and the in-kernel CRC segment helpers.  Used by decode_kernel
+// (dg_kernels.hip) and the in-place update kernel (dg_update_dev.hip, the
+// stand-alone code object lib/dg_update.hsaco).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -10,12 +11,9 @@
 #include "dg_device.h"
 #include "dg_devutil.h"
 #include "dg_crc.h"
+#include "dg_parse_chain.h"
 
 namespace dg {
-
-__device__ __forceinline__ uint32_t be32(const uint8_t* p) {
-	return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
-}
 
 // wave-wide memmove of len bytes (src and dst may overlap)
 __device__ void wave_memmove(uint8_t* dst, const uint8_t* src, uint64_t len) {
@@ -45,25 +43,28 @@ __device__ __forceinline__ bool overlap(uint64_t a, uint64_t al, uint64_t b, uin
 	return al && bl && a < b + bl && b < a + al;
 }
 
-// Command stream parsing (encoding.c:111-178) is a chain x -> x + |cmd(x)|
-// through the stream.  Per 4 KiB window of the stream (staged in LDS):
-//   1. every lane computes, for each window offset x it owns, the offset of the
-//      next command IF a command started at x (N1), or a code: END, malformed,
-//      header cut by the window, next command past the window;
-//   2. N2 = N1.N1, N4, N8, N16 by pointer doubling (codes propagate; N16
-//      takes N4's place once N8 is built);
-//   3. one uniform walk takes 16 commands per step through N16, then at most
-//      one N8 step and single steps near the window end; the nodes in between
-//      are expanded in parallel.
-// So a window of ~300 commands costs ~25 dependent LDS reads instead of ~300
-// serial header decodes.  The commands are then applied 64 at a time.
-#ifdef DG_ONEPASS_PROF   // profiling build only (make prof): per-phase decode cycles
+// profiling build only (make prof): per-phase decode cycles.  DP_LOAD..DP_EXP
+// are the parser's phases (ChainNoProf::chain) in its order.
 enum { DP_FILL, DP_LOAD, DP_N1, DP_DBL, DP_WALK, DP_EXP, DP_HDR, DP_COPY, DP_WAIT, DP_WINDOWS, DP_BATCHES, DP_TOTAL,
        DP_ORDERED, DP_C_CMD, DP_C_FLAT, DP_C_BAR, DP_CRC_SYNC, DP_CRC_SEG, DP_CRC_TAIL, kDecProfN };
+#ifdef DG_ONEPASS_PROF
 __device__ unsigned long long g_decode_prof[kDecProfN];
 #define DPROF_T(v) const uint64_t v = __builtin_amdgcn_s_memtime()
 #define DPROF_ADD(i, t0) (dprof[(i)] += __builtin_amdgcn_s_memtime() - (t0))
 #define DPROF_INC(i) (dprof[(i)] += 1)
+struct DecProf {   // the window step's hook: laps into the kernel's dprof
+	uint64_t* d;
+	uint64_t t;
+	__device__ __forceinline__ void start() { t = __builtin_amdgcn_s_memtime(); }
+	__device__ __forceinline__ void lap(uint32_t i) {
+		const uint64_t now = __builtin_amdgcn_s_memtime();
+		d[i] += now - t;
+		t = now;
+	}
+	__device__ __forceinline__ void chain(uint32_t k) { lap(DP_LOAD + k); }
+	__device__ __forceinline__ void count(uint32_t i) { d[i] += 1; }
+};
+#define DPROF_HOOK DecProf{dprof, 0}
 extern "C" int dg_decode_prof_read(unsigned long long* out, int n) {
 	if (n > kDecProfN) n = kDecProfN;
 	return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_decode_prof), 8 * n) == hipSuccess ? n : -1;
@@ -76,39 +77,13 @@ extern "C" int dg_decode_prof_reset(void) {
 #define DPROF_T(v) ((void)0)
 #define DPROF_ADD(i, t0) ((void)0)
 #define DPROF_INC(i) ((void)0)
+#define DPROF_HOOK ChainNoProf{}
 #endif
-
-constexpr uint32_t kDecWin = 4096;       // bytes of the command stream per window
-constexpr uint32_t kDecMaxCmds = 512;    // >= kDecWin / 9 (the shortest command)
-constexpr uint16_t kNxEnd = 0xFFFE;      // END at x
-constexpr uint16_t kNxBad = 0xFFFD;      // malformed at x
-constexpr uint16_t kNxCut = 0xFFFF;      // header not complete in the window: restart at x
-constexpr uint16_t kNxFar = 0xFFFC;      // complete command at x, next one at/after the window end
-constexpr uint16_t kNxSpecial = 0xFFFC;  // codes are >= this
-
-// inclusive prefix sum over the wave (DPP row shifts + row broadcasts)
-__device__ __forceinline__ uint32_t dec_incl_scan(uint32_t x) {
-	x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xF, 0xF, false);   // row_shr:1
-	x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xF, 0xF, false);   // row_shr:2
-	x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xF, 0xF, false);   // row_shr:4
-	x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xF, 0xF, false);   // row_shr:8
-	x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xA, 0xF, false);   // row_bcast:15
-	x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xC, 0xF, false);   // row_bcast:31
-	return x;
-}
-
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t x) {
-#pragma unroll
-	for (int d = 32; d >= 1; d >>= 1) {
-		const uint32_t y = (uint32_t)__shfl_xor((int)x, d, 64);
-		x = x > y ? x : y;
-	}
-	return x;
-}
 
 // ── decode: one 256-thread block (4 waves) per delta stream ──
 //
-// Per window: all four waves build N1..N8; wave 0 walks; all expand.  The
+// Per window (4 KiB of the stream, up to 512 commands): all four waves build
+// N1..N8; wave 0 walks; all expand (chain_window<256>, dg_parse_chain.h).  The
 // window's commands are then applied 64 per wave at a time, all four waves
 // at once, when the window is provably order-free: destinations increasing
 // and disjoint in stream order and no in-place COPY that moves (src == dst
@@ -117,6 +92,8 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t x) {
 // The block barrier between windows also orders every store of one window
 // before the next window's reads and writes.
 constexpr uint32_t kDecBlock = 256;
+constexpr uint32_t kDecWin = kChainWin<kDecBlock>;           // bytes of the command stream per window
+constexpr uint32_t kDecMaxCmds = kChainMaxCmds<kDecBlock>;   // commands per window
 constexpr uint32_t kDecCrcSeg = 16384;                // in-kernel CRC: 16 KiB segments
 static_assert(4 * kDecCrcSeg == kCrcSegBytes, "the Horner step (4 segments) is x^(8 kCrcSegBytes)");
 
@@ -144,20 +121,6 @@ __device__ __forceinline__ uint32_t hdr_be32(const uint32_t (&h)[4], int i) {
 	return __builtin_bswap32(__builtin_amdgcn_alignbyte(h[i + 1], h[i], 1));
 }
 
-// 16 window bytes at any offset as five aligned dwords and four funnel
-// shifts (an unaligned ds_read_b128 stalls the LDS pipe on gfx950,
-// profiles/r05_member_census.md; here decode_kernel 0.1115 -> 0.1088 ms at
-// C5); the window has 32 bytes of slack.
-__device__ __forceinline__ void win16(const uint8_t* p, uint32_t (&h)[4]) {
-	const uint32_t mis = (uint32_t)(uintptr_t)p & 3u;
-	const uint32_t* d = reinterpret_cast<const uint32_t*>(p - mis);
-	const uint32_t d0 = d[0], d1 = d[1], d2 = d[2], d3 = d[3], d4 = d[4], sh = 8u * mis;
-	h[0] = __builtin_amdgcn_alignbit(d1, d0, sh);
-	h[1] = __builtin_amdgcn_alignbit(d2, d1, sh);
-	h[2] = __builtin_amdgcn_alignbit(d3, d2, sh);
-	h[3] = __builtin_amdgcn_alignbit(d4, d3, sh);
-}
-
 // The window holds >= 16 bytes past any command offset (win has 32 bytes of
 // slack), so a header is one 16-byte read.
 template <typename WP>
@@ -182,10 +145,6 @@ __device__ __forceinline__ DecCmd dec_cmd(WP w, const uint16_t* cmds, uint32_t b
 	}
 	return c;
 }
-
-// unaligned dword / 16-byte accesses (gfx950 global memory allows them)
-typedef uint32_t u32x4_u __attribute__((ext_vector_type(4), aligned(1)));
-typedef uint32_t u32_u __attribute__((aligned(1)));
 
 // A command's last, partial 16-byte chunk (1 <= rem < 16 bytes).  Every load
 // is issued before any store, so the chunk costs one memory round trip: the
@@ -241,11 +200,11 @@ __device__ void dec_flat_batch(const DecCmd& c, bool inplace, uint8_t* O, const 
 	const bool noop = c.mine && c.kind == 1 && inplace && c.src == c.dst;
 	const uint32_t flen = (c.mine && !selfov && !noop) ? (uint32_t)c.len : 0u;
 	const uint32_t fch = (flen + 15u) >> 4;
-	const uint32_t incl = dec_incl_scan(fch);
+	const uint32_t incl = wave_incl_scan(fch);
 	const uint32_t cum = incl - fch;
 	const uint32_t total = rdlane(incl, 63);   // chunks
 	const bool nz = fch != 0;
-	const uint32_t ord = dec_incl_scan(nz ? 1u : 0u) - 1u;
+	const uint32_t ord = wave_incl_scan(nz ? 1u : 0u) - 1u;
 	if (nz) {
 		x.cum[ord] = cum;
 		x.sp[ord] = sp;
@@ -266,7 +225,7 @@ __device__ void dec_flat_batch(const DecCmd& c, bool inplace, uint8_t* O, const 
 		__builtin_amdgcn_wave_barrier();
 		const uint64_t mrow = ((uint64_t)x.row[64 + lane] << 32) | x.row[lane];   // row r0 + lane
 		const uint32_t pc = (uint32_t)__builtin_popcountll(mrow);
-		const uint32_t rbase = carry + dec_incl_scan(pc) - pc;   // starts before row r0 + lane
+		const uint32_t rbase = carry + wave_incl_scan(pc) - pc;   // starts before row r0 + lane
 		const uint32_t nrows = min(64u, (total + 63) / 64 - r0);
 		constexpr int kQ = 4;   // rows per pass (VGPR budget: 4 waves per SIMD)
 		for (uint32_t q0 = 0; q0 < nrows; q0 += kQ) {
@@ -368,7 +327,7 @@ __device__ void dec_grouped_window(WP w, const uint16_t* cmds, uint32_t cnt, uin
 	}
 	{
 		const uint32_t v = f2[0] + f2[1];
-		const uint32_t incl = dec_incl_scan(v);
+		const uint32_t incl = wave_incl_scan(v);
 		if (lane == 63) g.red[wave] = incl;
 		__syncthreads();
 		uint32_t off = 0;
@@ -498,6 +457,142 @@ __device__ void dec_grouped_window(WP w, const uint16_t* cmds, uint32_t cnt, uin
 		}
 		block_sync_global();   // the group's stores land before the next group reads or writes
 	}
+}
+
+// ── the block's LDS and the window step ──
+//
+// A kernel declares the seven arrays
+//   uint8_t win[kDecWin + 32], uint16_t N1[kDecWin], NX[3 * kDecWin]      (16-byte aligned)
+//   uint16_t cmds[kDecMaxCmds], jumps[kDecMaxCmds / 16 + 2]
+//   uint32_t sh[8], bsum[2 * (kDecMaxCmds / 64 + 1)]
+// and dec_lds carves them.  NX holds N2, N4, N8 during the parse; afterwards
+// the waves' flat-copy scratch, then the grouped apply's arrays (or, outside
+// the window loop, the CRC tables: dec_crc_tables).
+struct DecLds {
+	ChainLds ch;       // win, N1, N2..N8 (NX), cmds, jumps, sh ([0..3], [6]: the walk's result)
+	uint16_t* NX;
+	uint32_t* sh;      // [4]: a batch out of bounds, [5]: the window is not order-free
+	uint32_t* bsum;    // per batch of 64 commands: first written dst, max end
+	DecScratch xs;     // this wave's
+	DecGroupLds grp;
+};
+__device__ __forceinline__ DecLds dec_lds(uint8_t* win, uint16_t* N1, uint16_t* NX, uint16_t* cmds, uint16_t* jumps,
+                                          uint32_t* sh, uint32_t* bsum) {
+	constexpr uint32_t kScratch = 64 * 4 + 128 * 4 + 64 * 8 + 64 * 8 + 64 * 4;
+	static_assert(kDecWaves * kScratch <= 3 * kDecWin * 2, "scratch fits NX");
+	static_assert(kDecWaves * kScratch + 4 * (4 * kDecMaxCmds + 4 + 8) + 2 * (2 * kDecMaxCmds + 2) + kDecMaxCmds <=
+	                  3 * kDecWin * 2,
+	              "grouped-apply arrays fit NX");
+	DecLds L;
+	L.ch = ChainLds{N1, NX, NX + kDecWin, NX + 2 * kDecWin, win, cmds, jumps, sh};
+	L.NX = NX;
+	L.sh = sh;
+	L.bsum = bsum;
+	uint8_t* base = reinterpret_cast<uint8_t*>(NX) + (threadIdx.x >> 6) * kScratch;
+	L.xs.sp = reinterpret_cast<const uint8_t**>(base);
+	L.xs.dp = reinterpret_cast<uint8_t**>(base + 64 * 8);
+	L.xs.cum = reinterpret_cast<uint32_t*>(base + 128 * 8);
+	L.xs.row = reinterpret_cast<uint32_t*>(base + 128 * 8 + 64 * 4);
+	L.xs.len = reinterpret_cast<uint32_t*>(base + 128 * 8 + 64 * 4 + 128 * 4);
+	DecGroupLds& g = L.grp;   // after the four waves' flat-copy scratch
+	g.src = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(NX) + kDecWaves * kScratch);
+	g.dst = g.src + kDecMaxCmds;
+	g.len = g.dst + kDecMaxCmds;
+	g.pre = g.len + kDecMaxCmds;                                  // kDecMaxCmds + 1 (+3 pad)
+	g.red = g.pre + kDecMaxCmds + 4;                              // 8
+	g.last = reinterpret_cast<int16_t*>(g.red + 8);               // kDecMaxCmds
+	g.gs = reinterpret_cast<uint16_t*>(g.last + kDecMaxCmds);     // kDecMaxCmds + 1 (+1 pad)
+	g.flag = reinterpret_cast<uint8_t*>(g.gs + kDecMaxCmds + 2);
+	return L;
+}
+
+// The window at pos to LDS: the aligned 16-byte blocks that hold stream bytes
+// (a block never crosses a page); returns shf, win[shf + x] = D[pos + x].
+// The caller puts a barrier after it (chain_window begins with one).
+__device__ __forceinline__ uint32_t dec_load_window(uint8_t* win, const uint8_t* D, uint64_t dl, uint64_t pos) {
+	const uintptr_t wa = (uintptr_t)(D + pos) & ~(uintptr_t)15;
+	const uintptr_t dend = (uintptr_t)(D + dl);
+	for (uint32_t q = threadIdx.x; q < (kDecWin + 32) / 16; q += kDecBlock) {
+		const uintptr_t ad = wa + 16 * q;
+		uint4 x = make_uint4(0, 0, 0, 0);
+		if (ad < dend) x = *reinterpret_cast<const uint4*>(ad);
+		reinterpret_cast<uint4*>(win)[q] = x;
+	}
+	return (uint32_t)((uintptr_t)(D + pos) - wa);
+}
+
+struct DecWin {
+	uint32_t cnt;        // commands of the window, their offsets in cmds
+	uint32_t shf;        // win + shf is the window's first stream byte
+	uint64_t next_pos;   // where the next window starts
+	bool done;           // END seen
+	bool bad;            // malformed, or a command out of bounds
+	bool free_win;       // order-free: applied flat
+};
+
+// One window of the stream at pos < dl (a command boundary): the window to
+// LDS, its command chain, and the bounds (dst + len <= lim_dst, a COPY's
+// src + len <= lim_src) and order checks of every batch of 64 commands.
+// Every thread returns the same values.  The caller puts a block barrier
+// between two calls.
+template <class Prof = ChainNoProf>
+__device__ __forceinline__ DecWin dec_window(const DecLds& L, const uint8_t* D, uint64_t dl, uint64_t pos, bool inplace,
+                                             uint64_t lim_dst, uint64_t lim_src, Prof&& pf = Prof()) {
+	const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = lane_id();
+	DecWin r{};
+	pf.count(DP_WINDOWS);
+	pf.start();
+	if (tid == 0) L.sh[4] = L.sh[5] = 0;
+	r.shf = dec_load_window(L.ch.win, D, dl, pos);
+	const uint8_t* w = L.ch.win + r.shf;
+	const auto cw = chain_window<kDecBlock>(L.ch, w, (uint32_t)min((uint64_t)kDecWin, dl - pos), pos, dl, pf);
+	r.cnt = cw.cnt;
+	r.next_pos = cw.next_pos;
+	r.done = cw.term == kChEnd;
+	r.bad = cw.term == kChBad;
+	// bounds and order checks of every batch (waves in parallel)
+	const uint32_t nb = (r.cnt + 63) / 64;
+	for (uint32_t b = wave; b < nb; b += kDecWaves) {
+		const DecCmd c = dec_cmd(w, L.ch.cmds, 64 * b, r.cnt, pos);
+		bool bad = false;
+		if (c.mine) {
+			if (c.dst + c.len > lim_dst) bad = true;
+			if (c.kind == 1 && c.src + c.len > lim_src) bad = true;
+		}
+		// order-free: the commands that write (an in-place COPY with src ==
+		// dst writes nothing: apply.c:257-266 memmoves a range onto itself,
+		// and the in-place format puts the ADDs after the COPYs,
+		// inplace.c:711-725) have increasing, disjoint destinations (< 2^32:
+		// lim_dst checked), and no in-place COPY moves.  Within the batch by a
+		// prefix max of the write ends; across batches by the summaries.
+		const bool writes = c.mine && c.len != 0 && !(inplace && c.kind == 1 && c.src == c.dst);
+		const uint32_t end32 = writes ? (uint32_t)(c.dst + c.len) : 0u, dst32 = (uint32_t)c.dst;
+		const uint32_t incl_end = wave_incl_max(end32);
+		const bool unordered = writes && dst32 < wave_shr1z(incl_end);
+		const bool moves = c.mine && inplace && c.kind == 1 && c.src != c.dst;
+		const uint64_t wm = __ballot(writes);
+		const uint32_t first_dst = wm ? rdlane(dst32, ffs64(wm)) : ~0u;
+		if (lane == 0) {
+			L.bsum[2 * b] = first_dst;
+			L.bsum[2 * b + 1] = rdlane(incl_end, 63);
+		}
+		if (__ballot(bad) && lane == 0) atomicOr(&L.sh[4], 1u);
+		if (__ballot(unordered || moves) && lane == 0) atomicOr(&L.sh[5], 1u);
+	}
+	__syncthreads();
+	if (L.sh[4]) r.bad = true;
+	bool cross = false;   // a batch writes below the end of an earlier batch's writes
+	for (uint32_t b = 0, run = 0; b < nb; ++b) {
+		const uint32_t f = L.bsum[2 * b], e = L.bsum[2 * b + 1];
+		if (f != ~0u) {
+			cross = cross || f < run;
+			run = umax32(run, e);
+		}
+	}
+	r.free_win = !L.sh[5] && !cross;
+	if (!r.free_win) pf.count(DP_ORDERED);
+	pf.lap(DP_HDR);
+	return r;
 }
 
 // The decode kernel's CRC segments: 16 KiB segments as rows of 64 x 8 bytes

@@ -38,8 +38,6 @@ using namespace dgip;
 
 namespace {
 
-typedef uint32_t u32_u __attribute__((aligned(1)));
-
 constexpr uint32_t kLdsWords = 2048;       // dst column cache; radix counters; small graph / ready bitmap
 constexpr uint32_t kSmallGraph = 128;      // copies up to which the Kahn loop and the stall code run out of LDS
 
@@ -240,7 +238,7 @@ extern "C" __global__ __launch_bounds__(64) void dg_inplace_order_kernel(IpArgs 
 	const uint32_t dl = (uint32_t)s_len;
 	res.stream_off = s_off;
 	res.stream_len = dl;
-	if (dl < 25 || D[0] != 'D' || D[1] != 'L' || D[2] != 'T' || D[3] != 3) return finish(8, 0);
+	if (bad_magic(D, dl)) return finish(8, 0);
 	if (D[4] & 1) {   // already in-place: unchanged
 		res.passthrough = 1;
 		return finish(0, dl);
@@ -259,7 +257,7 @@ extern "C" __global__ __launch_bounds__(64) void dg_inplace_order_kernel(IpArgs 
 	bool bad = false, unsup = false, full = false, ended = false;
 	while (!ended && !bad) {
 		if (pos >= dl) break;   // the stream ends without an END byte (encoding.c:111-178 allows it)
-		const ChainWindow cw = chain_window(D, dl, pos, cl);
+		const auto cw = chain_window<64>(cl, cl.win, chain_load_wave(cl.win, D, dl, pos), pos, dl);
 		const uint32_t cnt = cw.cnt;
 		for (uint32_t b0 = 0; b0 < cnt; b0 += 64) {
 			const bool mine = b0 + lane < cnt;
@@ -270,12 +268,12 @@ extern "C" __global__ __launch_bounds__(64) void dg_inplace_order_kernel(IpArgs 
 				cx = cmds[b0 + lane];
 				kind = win[cx];
 				if (kind == 1) {
-					c_src = be32_at(win + cx + 1);
-					c_dst = be32_at(win + cx + 5);
-					c_len = be32_at(win + cx + 9);
+					c_src = be32(win + cx + 1);
+					c_dst = be32(win + cx + 5);
+					c_len = be32(win + cx + 9);
 				} else {
-					c_dst = be32_at(win + cx + 1);
-					c_len = be32_at(win + cx + 5);
+					c_dst = be32(win + cx + 1);
+					c_len = be32(win + cx + 5);
 				}
 			}
 			const bool is_copy = mine && kind == 1, is_add = mine && kind == 2;
@@ -471,7 +469,7 @@ extern "C" __global__ __launch_bounds__(256) void dg_inplace_emit_kernel(IpArgs 
 			const uint32_t so = w.add_off[k];
 			sp = D + so;
 			dp = OA + w.add_out[k];
-			nb = 9 + be32_at(D + so + 5);
+			nb = 9 + be32(D + so + 5);
 		} else if (k < nadd + nv) {
 			const uint32_t kk = k - nadd, v = w.order[n - 1 - kk];
 			dp = OV + w.indeg[kk];

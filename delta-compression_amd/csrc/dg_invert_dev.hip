@@ -42,20 +42,6 @@ using namespace dgiv;
 
 namespace {
 
-// 1 + the nearest earlier lane whose flag is set, 0 when there is none
-__device__ __forceinline__ uint32_t prev_set(bool f, uint32_t lane) {
-	return wave_shr1z(wave_incl_max(f ? lane + 1u : 0u));
-}
-// 1 + the last lane whose flag is set, 0 when there is none (uniform)
-__device__ __forceinline__ uint32_t last_set(bool f) {
-	const uint64_t m = __ballot(f);
-	return m ? 64u - (uint32_t)__builtin_clzll(m) : 0u;
-}
-__device__ __forceinline__ uint32_t shfl32(uint32_t x, uint32_t l) { return (uint32_t)__shfl((int)x, (int)(l & 63u), 64); }
-__device__ __forceinline__ uint64_t shfl64(uint64_t x, uint32_t l) {
-	return ((uint64_t)shfl32((uint32_t)(x >> 32), l) << 32) | shfl32((uint32_t)x, l);
-}
-
 struct Work {
 	IvRec* rec[2];    // C each
 	IvEmit* emit;     // C + 1
@@ -162,18 +148,18 @@ extern "C" __global__ __launch_bounds__(64) void dg_invert_map_kernel(IvArgs a) 
 
 	// ── the stream: validate, one record per non-empty COPY ──
 	uint32_t nC = 0;
-	if (dl < 25 || S[0] != 'D' || S[1] != 'L' || S[2] != 'T' || S[3] != 3) {
+	if (bad_magic(S, dl)) {
 		bad = true;
 	} else {
 		if (S[4] & 1) unsup = true;
-		const uint32_t vs = be32_at(S + 5);
+		const uint32_t vs = be32(S + 5);
 		uint32_t pos = 25;
 		uint64_t wpos = 0;
 		bool c_has = false, ended = false;   // the last record so far: its key
 		uint64_t c_key = 0;
 		while (!ended && !bad) {
 			if (pos >= dl) break;   // the stream ends without an END byte
-			const ChainWindow cw = chain_window(S, dl, pos, cl);
+			const auto cw = chain_window<64>(cl, cl.win, chain_load_wave(cl.win, S, dl, pos), pos, dl);
 			for (uint32_t b0 = 0; b0 < cw.cnt; b0 += 64) {
 				const bool mine = b0 + lane < cw.cnt;
 				const Hdr h = decode_hdr(win, cmds, b0 + lane, mine);

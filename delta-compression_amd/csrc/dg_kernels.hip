@@ -484,37 +484,7 @@ __global__ __launch_bounds__(kDecBlock) __attribute__((amdgpu_waves_per_eu(4, 8)
 	__shared__ uint32_t bsum[2 * (kDecMaxCmds / 64 + 1)];   // per batch: first written dst, max end
 	__shared__ uint64_t cpart[2][kDecWaves];   // crc_check: per span, each wave's Horner partial
 	__shared__ uint32_t clast[2][kDecWaves];   // and its last segment
-	uint16_t* N2 = NX;
-	uint16_t* N4 = NX + kDecWin;
-	uint16_t* N8 = NX + 2 * kDecWin;
-	uint16_t* N16 = N4;   // (N4 is dead once N8 is built)
-	constexpr uint32_t kScratch = 64 * 4 + 128 * 4 + 64 * 8 + 64 * 8 + 64 * 4;
-	static_assert(kDecWaves * kScratch <= 3 * kDecWin * 2, "scratch fits NX");
-	DecScratch xs;
-	{
-		uint8_t* base = reinterpret_cast<uint8_t*>(NX) + wave * kScratch;
-		xs.sp = reinterpret_cast<const uint8_t**>(base);
-		xs.dp = reinterpret_cast<uint8_t**>(base + 64 * 8);
-		xs.cum = reinterpret_cast<uint32_t*>(base + 128 * 8);
-		xs.row = reinterpret_cast<uint32_t*>(base + 128 * 8 + 64 * 4);
-		xs.len = reinterpret_cast<uint32_t*>(base + 128 * 8 + 64 * 4 + 128 * 4);
-	}
-	// the grouped apply's arrays, after the four waves' flat-copy scratch
-	DecGroupLds grp;
-	{
-		uint8_t* base = reinterpret_cast<uint8_t*>(NX) + kDecWaves * kScratch;
-		grp.src = reinterpret_cast<uint32_t*>(base);
-		grp.dst = grp.src + kDecMaxCmds;
-		grp.len = grp.dst + kDecMaxCmds;
-		grp.pre = grp.len + kDecMaxCmds;                     // kDecMaxCmds + 1 (+3 pad)
-		grp.red = grp.pre + kDecMaxCmds + 4;                 // 8
-		grp.last = reinterpret_cast<int16_t*>(grp.red + 8);  // kDecMaxCmds
-		grp.gs = reinterpret_cast<uint16_t*>(grp.last + kDecMaxCmds);   // kDecMaxCmds + 1 (+1 pad)
-		grp.flag = reinterpret_cast<uint8_t*>(grp.gs + kDecMaxCmds + 2);
-		static_assert(kDecWaves * kScratch + 4 * (4 * kDecMaxCmds + 4 + 8) + 2 * (2 * kDecMaxCmds + 2) + kDecMaxCmds <=
-		                  3 * kDecWin * 2,
-		              "grouped-apply arrays fit NX");
-	}
+	const DecLds L = dec_lds(win, N1, NX, cmds, jumps, sh, bsum);
 
 #ifdef DG_ONEPASS_PROF
 	uint64_t dprof[kDecProfN] = {};
@@ -529,7 +499,7 @@ __global__ __launch_bounds__(kDecBlock) __attribute__((amdgpu_waves_per_eu(4, 8)
 
 	int32_t st = 0;
 	uint64_t vsize = 0;
-	if (dl < 25 || D[0] != 'D' || D[1] != 'L' || D[2] != 'T' || D[3] != 3) st = 8;
+	if (bad_magic(D, dl)) st = 8;
 	bool inplace = false;
 	if (!st) {
 		inplace = D[4] & 1;
@@ -600,215 +570,16 @@ __global__ __launch_bounds__(kDecBlock) __attribute__((amdgpu_waves_per_eu(4, 8)
 	bool done = false;
 	while (!done && !st) {
 		if (pos >= dl) break;   // missing END: end of input (as the reference's loop)
-		const uint32_t avail = (uint32_t)min((uint64_t)kDecWin, dl - pos);
-		// ── 1. window -> LDS: aligned 16-byte blocks that hold stream bytes
-		//    (a block never crosses a page), win[sh + x] = D[pos + x]
-		const uintptr_t wa = (uintptr_t)(D + pos) & ~(uintptr_t)15;
-		const uint32_t shf = (uint32_t)((uintptr_t)(D + pos) - wa);
-		const uintptr_t dend = (uintptr_t)(D + dl);
-		DPROF_INC(DP_WINDOWS);
-		DPROF_T(tl0);
-		for (uint32_t q = tid; q < (kDecWin + 32) / 16; q += kDecBlock) {
-			const uintptr_t ad = wa + 16 * q;
-			uint4 x = make_uint4(0, 0, 0, 0);
-			if (ad < dend) x = *reinterpret_cast<const uint4*>(ad);
-			reinterpret_cast<uint4*>(win)[q] = x;
-		}
-		__syncthreads();
-		const uint8_t* w = win + shf;
-		DPROF_ADD(DP_LOAD, tl0);
-		DPROF_T(tn0);
-		// ── 2. N1: next command offset for a command starting at x.  Thread
-		//    tid owns offsets [16 tid, 16 tid + 16): all default to malformed
-		//    (two 16-byte stores), and only offsets whose byte is a command
-		//    type (0, 1, 2: ~1.3 of 16 in a command stream) are decoded ──
-		static_assert(kDecWin == 16 * kDecBlock, "16 window offsets per thread");
-		{
-			const uint32_t x0 = 16 * tid;
-			constexpr uint32_t bb = (uint32_t)kNxBad | ((uint32_t)kNxBad << 16);
-			uint4* dst = reinterpret_cast<uint4*>(N1 + x0);
-			dst[0] = make_uint4(bb, bb, bb, bb);
-			dst[1] = make_uint4(bb, bb, bb, bb);
-			uint32_t d[4];
-			win16(w + x0, d);
-			uint32_t cand = 0;
-#pragma unroll
-			for (uint32_t k = 0; k < 16; ++k) cand |= (((d[k >> 2] >> (8 * (k & 3))) & 0xFFu) <= 2u ? 1u : 0u) << k;
-			const uint32_t lim = avail > x0 ? umin32(avail - x0, 16u) : 0u;
-			cand &= (1u << lim) - 1u;
-			for (; cand; cand &= cand - 1) {
-				const uint32_t x = x0 + (uint32_t)__builtin_ctz(cand);
-				const uint32_t t = w[x];
-				uint32_t nx = kNxEnd;
-				if (t != 0) {
-					const uint32_t hdr = t == 1 ? 13u : 9u;
-					if (x + hdr > avail) {
-						nx = pos + x + hdr > dl ? kNxBad : kNxCut;
-					} else {
-						uint32_t lw = 0;
-						__builtin_memcpy(&lw, w + x + 5, 4);
-						const uint64_t len = t == 1 ? 0 : __builtin_bswap32(lw);
-						const uint64_t end = (uint64_t)x + hdr + len;
-						if (pos + end > dl) nx = kNxBad;
-						else nx = end >= avail ? kNxFar : (uint32_t)end;
-					}
-				}
-				N1[x] = (uint16_t)nx;
-			}
-		}
-		__syncthreads();
-		DPROF_ADD(DP_N1, tn0);
-		DPROF_T(td0);
-		// ── 3. pointer doubling ──
-		// (16 offsets per thread: two 16-byte reads, 16 independent gathers,
-		// two 16-byte stores)
-		auto dbl = [&](const uint16_t* src, uint16_t* dstN) {
-			const uint32_t x0 = 16 * tid;
-			const uint4* sp = reinterpret_cast<const uint4*>(src + x0);
-			const uint4 a = sp[0], b = sp[1];
-			const uint32_t in[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-			uint32_t o[8];
-#pragma unroll
-			for (uint32_t k = 0; k < 8; ++k) {
-				const uint32_t y0 = in[k] & 0xFFFFu, y1 = in[k] >> 16;
-				const uint32_t z0 = y0 >= kNxSpecial ? y0 : src[y0];
-				const uint32_t z1 = y1 >= kNxSpecial ? y1 : src[y1];
-				o[k] = z0 | (z1 << 16);
-			}
-			uint4* dp = reinterpret_cast<uint4*>(dstN + x0);
-			dp[0] = make_uint4(o[0], o[1], o[2], o[3]);
-			dp[1] = make_uint4(o[4], o[5], o[6], o[7]);
-		};
-		dbl(N1, N2);
-		__syncthreads();
-		dbl(N2, N4);
-		__syncthreads();
-		dbl(N4, N8);
-		__syncthreads();
-		dbl(N8, N16);
-		__syncthreads();
-		DPROF_ADD(DP_DBL, td0);
-		DPROF_T(tw0);
-		// ── 4. the walk (wave 0, uniform): 16 commands per N16 step, at most
-		//    one N8 step, then single steps ──
-		if (wave == 0) {
-			uint32_t x = 0, nj = 0, n8 = 0;
-			uint32_t term = 0;
-			while (true) {
-				const uint32_t y = uni(N16[x]);
-				if (y >= kNxSpecial || 16 * (nj + 1) > kDecMaxCmds) break;
-				if (lane == 0) jumps[nj] = (uint16_t)x;
-				++nj;
-				x = y;
-			}
-			uint32_t cnt = 16 * nj;
-			{
-				const uint32_t y = uni(N8[x]);
-				if (y < kNxSpecial && cnt + 8 <= kDecMaxCmds) {
-					if (lane == 0) jumps[nj] = (uint16_t)x;
-					n8 = 1;
-					cnt += 8;
-					x = y;
-				}
-			}
-			while (true) {   // single steps from x (at most 7 commands + the terminal)
-				const uint32_t y = uni(N1[x]);
-				if (y == kNxEnd || y == kNxBad || y == kNxCut) { term = y; break; }
-				if (cnt >= kDecMaxCmds) { term = kNxCut; break; }   // restart the window at x
-				if (lane == 0) cmds[cnt] = (uint16_t)x;
-				++cnt;
-				if (y == kNxFar) { term = kNxFar; break; }
-				x = y;
-			}
-			if (lane == 0) {
-				sh[0] = cnt;
-				sh[1] = nj;
-				sh[2] = x;
-				sh[3] = term;
-				sh[4] = 0;   // a batch out of bounds
-				sh[5] = 0;   // the window is not order-free
-				sh[6] = n8;
-			}
-		}
-		__syncthreads();
-		const uint32_t cnt = sh[0], nj = sh[1], x = sh[2], term = sh[3], n8 = sh[6];
-		DPROF_ADD(DP_WALK, tw0);
-		DPROF_T(te0);
-		// expand the jumps: 8 nodes from each base (e, N1 e, N2 e, ..., N1 N2 N2 N2 e);
-		// a 16-command jump has bases e and N8 e
-		for (uint32_t k = tid; k < 2 * nj + n8; k += kDecBlock) {
-			const uint32_t j = k >> 1;
-			const uint32_t e0 = j < nj ? ((k & 1) ? N8[jumps[j]] : jumps[j]) : jumps[nj];
-			const uint32_t e2 = N2[e0];
-			const uint32_t e4 = N2[e2];
-			const uint32_t e6 = N2[e4];
-			uint16_t* c = cmds + (j < nj ? 16 * j + 8 * (k & 1) : 16 * nj);
-			c[0] = (uint16_t)e0;
-			c[1] = N1[e0];
-			c[2] = (uint16_t)e2;
-			c[3] = N1[e2];
-			c[4] = (uint16_t)e4;
-			c[5] = N1[e4];
-			c[6] = (uint16_t)e6;
-			c[7] = N1[e6];
-		}
-		__syncthreads();   // cmds complete; N2..N8 dead: NX becomes the copy scratch
-		DPROF_ADD(DP_EXP, te0);		// the walk's terminal: x is where it stopped
-		uint64_t next_pos = pos + x;   // kNxCut: restart at x
-		if (term == kNxEnd) done = true;
-		else if (term == kNxBad) st = 8;
-		else if (term == kNxFar) {
-			const uint32_t t = w[x];
-			next_pos = pos + x + (t == 1 ? 13u : 9u + be32(w + x + 5));
-		}
-
-		// ── 5. bounds and order checks of every batch (waves in parallel) ──
-		DPROF_T(th0);
-		const uint32_t nb = (cnt + 63) / 64;
-		for (uint32_t b = wave; b < nb; b += kDecWaves) {
-			const DecCmd c = dec_cmd(w, cmds, 64 * b, cnt, pos);
-			bool bad = false;
-			if (c.mine) {
-				if (c.dst + c.len > bsz) bad = true;
-				if (c.kind == 1 && c.src + c.len > (inplace ? bsz : rl)) bad = true;
-			}
-			// order-free: the commands that write (an in-place COPY with src ==
-			// dst writes nothing: apply.c:257-266 memmoves a range onto itself,
-			// and the in-place format puts the ADDs after the COPYs,
-			// inplace.c:711-725) have increasing, disjoint destinations (< 2^32:
-			// bsz checked), and no in-place COPY moves.  Within the batch by a
-			// prefix max of the write ends; across batches by the summaries.
-			const bool writes = c.mine && c.len != 0 && !(inplace && c.kind == 1 && c.src == c.dst);
-			const uint32_t end32 = writes ? (uint32_t)(c.dst + c.len) : 0u, dst32 = (uint32_t)c.dst;
-			const uint32_t incl_end = wave_incl_max(end32);
-			const bool unordered = writes && dst32 < wave_shr1z(incl_end);
-			const bool moves = c.mine && inplace && c.kind == 1 && c.src != c.dst;
-			const uint64_t wm = __ballot(writes);
-			const uint32_t first_dst = wm ? rdlane(dst32, ffs64(wm)) : ~0u;
-			if (lane == 0) {
-				bsum[2 * b] = first_dst;
-				bsum[2 * b + 1] = rdlane(incl_end, 63);
-			}
-			if (__ballot(bad) && lane == 0) atomicOr(&sh[4], 1u);
-			if (__ballot(unordered || moves) && lane == 0) atomicOr(&sh[5], 1u);
-		}
-		__syncthreads();
-		if (sh[4]) st = 8;
-		bool cross = false;   // a batch writes below the end of an earlier batch's writes
-		for (uint32_t b = 0, run = 0; b < nb; ++b) {
-			const uint32_t f = bsum[2 * b], e = bsum[2 * b + 1];
-			if (f != ~0u) {
-				cross = cross || f < run;
-				run = umax32(run, e);
-			}
-		}
-		const bool free_win = !sh[5] && !cross;
-		if (!free_win) DPROF_INC(DP_ORDERED);
-		DPROF_ADD(DP_HDR, th0);
+		// ── 1-5. the window: load, command chain, bounds and order checks ──
+		const DecWin W = dec_window(L, D, dl, pos, inplace, bsz, inplace ? bsz : rl, DPROF_HOOK);
+		const uint8_t* w = win + W.shf;
+		const uint32_t cnt = W.cnt, nb = (cnt + 63) / 64;
+		done = W.done;
+		if (W.bad) st = 8;
 		DPROF_T(tc0);
 		// ── 6. apply ──
 		if (!st) {
-			if (free_win) {
+			if (W.free_win) {
 				for (uint32_t b = wave; b < nb; b += kDecWaves) {
 					DPROF_INC(DP_BATCHES);
 					DPROF_T(tq0);
@@ -818,18 +589,18 @@ __global__ __launch_bounds__(kDecBlock) __attribute__((amdgpu_waves_per_eu(4, 8)
 #endif
 					DPROF_ADD(DP_C_CMD, tq0);
 					DPROF_T(tq1);
-					dec_flat_batch(c, inplace, O, R, D, xs);
+					dec_flat_batch(c, inplace, O, R, D, L.xs);
 					DPROF_ADD(DP_C_FLAT, tq1);
 				}
 			} else {
-				dec_grouped_window(w, cmds, cnt, pos, inplace, O, R, D, grp);
+				dec_grouped_window(w, cmds, cnt, pos, inplace, O, R, D, L.grp);
 			}
 		}
 		DPROF_T(tq2);
 		block_sync_global();   // the window's stores complete before the next window
 		DPROF_ADD(DP_C_BAR, tq2);
 		DPROF_ADD(DP_COPY, tc0);
-		pos = next_pos;
+		pos = W.next_pos;
 	}
 	// ── 7. CRC-64/XZ of R and of the output, checked against the header
 	//    (main.c:341-356 before the apply, :376-385 after; a source mismatch
@@ -936,8 +707,5 @@ hipError_t launch_decode(const DecodeArgs& a, hipStream_t st) {
 	if (a.n) hipLaunchKernelGGL(decode_kernel, dim3(a.n), dim3(kDecBlock), 0, st, a);
 	return hipGetLastError();
 }
-
-
-
 
 }  // namespace dg

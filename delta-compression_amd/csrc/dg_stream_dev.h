@@ -1,7 +1,8 @@
 // dg_stream_dev.h — what the kernels that read and write whole delta streams
-// share (dg_inplace_dev.hip, dg_compose_dev.hip, dg_invert_dev.hip): big-endian fields, the
-// lane-owned command header of the parser's window (dg_parse_chain.h), a 64-bit
-// wave scan and the emit kernels' wave copy.  Device code only.
+// share (decode, update, in-place, compose, invert): the stream magic, big-endian
+// fields, unaligned access types, the lane-owned command header of the parser's
+// window (dg_parse_chain.h), wave scans and shuffles, and the emit kernels' wave
+// copy.  Device code only.
 #pragma once
 #include <stdint.h>
 
@@ -9,18 +10,25 @@
 
 namespace dg {
 
+// unaligned dword / 16-byte accesses (gfx950 global memory allows them)
 typedef uint32_t u32x4_u __attribute__((ext_vector_type(4), aligned(1)));
+typedef uint32_t u32_u __attribute__((aligned(1)));
 
 constexpr uint32_t kSmallCopy = 64;   // emit: spans up to this many bytes are one thread's
 
-// orders LDS and global memory between the lanes of the (one-wave) block
+// orders LDS and global memory between the lanes of a wave
 __device__ __forceinline__ void wave_sync() {
 	__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
 	__builtin_amdgcn_wave_barrier();
 }
 
-__device__ __forceinline__ uint32_t be32_at(const uint8_t* p) {
+__device__ __forceinline__ uint32_t be32(const uint8_t* p) {
 	return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
+}
+
+// not a DLT\x03 stream: shorter than the 25-byte header, or another magic
+__device__ __forceinline__ bool bad_magic(const uint8_t* S, uint64_t len) {
+	return len < 25 || S[0] != 'D' || S[1] != 'L' || S[2] != 'T' || S[3] != 3;
 }
 
 __device__ __forceinline__ void put_be32(uint8_t* p, uint32_t x) {
@@ -37,6 +45,20 @@ __device__ __forceinline__ uint64_t wave_excl_scan64(uint32_t x, uint64_t* total
 	return ((uint64_t)hi << 16) + lo - x;
 }
 
+// 1 + the nearest earlier lane whose flag is set, 0 when there is none
+__device__ __forceinline__ uint32_t prev_set(bool f, uint32_t lane) {
+	return wave_shr1z(wave_incl_max(f ? lane + 1u : 0u));
+}
+// 1 + the last lane whose flag is set, 0 when there is none (uniform)
+__device__ __forceinline__ uint32_t last_set(bool f) {
+	const uint64_t m = __ballot(f);
+	return m ? 64u - (uint32_t)__builtin_clzll(m) : 0u;
+}
+__device__ __forceinline__ uint32_t shfl32(uint32_t x, uint32_t l) { return (uint32_t)__shfl((int)x, (int)(l & 63u), 64); }
+__device__ __forceinline__ uint64_t shfl64(uint64_t x, uint32_t l) {
+	return ((uint64_t)shfl32((uint32_t)(x >> 32), l) << 32) | shfl32((uint32_t)x, l);
+}
+
 // one command's fields, decoded from the parser's window by its lane
 struct Hdr {
 	uint32_t cx, kind, src, dst, len;
@@ -47,12 +69,12 @@ __device__ __forceinline__ Hdr decode_hdr(const uint8_t* win, const uint16_t* cm
 		h.cx = cmds[k];
 		h.kind = win[h.cx];
 		if (h.kind == 1) {
-			h.src = be32_at(win + h.cx + 1);
-			h.dst = be32_at(win + h.cx + 5);
-			h.len = be32_at(win + h.cx + 9);
+			h.src = be32(win + h.cx + 1);
+			h.dst = be32(win + h.cx + 5);
+			h.len = be32(win + h.cx + 9);
 		} else {
-			h.dst = be32_at(win + h.cx + 1);
-			h.len = be32_at(win + h.cx + 5);
+			h.dst = be32(win + h.cx + 1);
+			h.len = be32(win + h.cx + 5);
 		}
 	}
 	return h;

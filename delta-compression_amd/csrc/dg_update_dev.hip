@@ -8,8 +8,8 @@
 // 111-178, and checks the source CRC, main.c:341-356, before it applies):
 //
 //   A  read only: header, capacity, every window of the command chain parsed
-//      and every command's bounds checked (the window parser of decode_kernel,
-//      dg_decode_dev.h), then R's CRC-64/XZ over the buffer.  One block-
+//      and every command's bounds checked (dec_window, dg_decode_dev.h, which
+//      decode_kernel calls too), then R's CRC-64/XZ over the buffer.  One block-
 //      uniform status; nonzero ends the block with the buffer untouched.
 //   B  [ref_len, bsz) zeroed (apply.c:276-278), then the stream is applied
 //      window by window as decode_kernel applies an in-place stream: order-
@@ -36,225 +36,7 @@ using namespace dgup;
 
 namespace {
 
-static_assert(kUpBlock == kDecBlock, "the window parser is written for decode's block");
-
-struct UpLds {
-	uint8_t* win;      // [kDecWin + 32]
-	uint16_t* N1;      // [kDecWin]
-	uint16_t* NX;      // [3 kDecWin]: N2, N4, N8 during the parse; scratch or CRC tables otherwise
-	uint16_t* cmds;    // [kDecMaxCmds]
-	uint16_t* jumps;   // [kDecMaxCmds / 16 + 2]
-	uint32_t* sh;      // [8]
-	uint32_t* bsum;    // [2 (kDecMaxCmds / 64 + 1)]
-};
-
-struct UpWin {
-	uint32_t cnt;        // commands of the window, their offsets in cmds
-	uint32_t shf;        // win + shf is the window's first stream byte
-	uint64_t next_pos;   // where the next window starts
-	bool done;           // END seen
-	bool bad;            // malformed, or a command out of bounds
-	bool free_win;       // order-free: applied flat
-};
-
-// One window of the stream at pos (a command boundary): the steps 1-5 of
-// decode_kernel (window to LDS, N1, pointer doubling, the walk and its
-// expansion, the bounds and order checks of every batch of 64 commands).
-// Every thread returns the same values.  The caller puts a block barrier
-// between two calls.
-__device__ __forceinline__ UpWin up_window(const UpLds& L, const uint8_t* D, uint64_t dl, uint64_t pos, bool inplace,
-                                           uint64_t lim_dst, uint64_t lim_src) {
-	const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = lane_id();
-	uint8_t* win = L.win;
-	uint16_t* N1 = L.N1;
-	uint16_t* N2 = L.NX;
-	uint16_t* N4 = L.NX + kDecWin;
-	uint16_t* N8 = L.NX + 2 * kDecWin;
-	uint16_t* N16 = N4;   // (N4 is dead once N8 is built)
-	uint16_t* cmds = L.cmds;
-	uint16_t* jumps = L.jumps;
-	uint32_t* sh = L.sh;
-	uint32_t* bsum = L.bsum;
-	UpWin r{};
-	const uint32_t avail = (uint32_t)min((uint64_t)kDecWin, dl - pos);
-	// 1. window -> LDS: the aligned 16-byte blocks that hold stream bytes
-	const uintptr_t wa = (uintptr_t)(D + pos) & ~(uintptr_t)15;
-	const uint32_t shf = (uint32_t)((uintptr_t)(D + pos) - wa);
-	const uintptr_t dend = (uintptr_t)(D + dl);
-	for (uint32_t q = tid; q < (kDecWin + 32) / 16; q += kDecBlock) {
-		const uintptr_t ad = wa + 16 * q;
-		uint4 x = make_uint4(0, 0, 0, 0);
-		if (ad < dend) x = *reinterpret_cast<const uint4*>(ad);
-		reinterpret_cast<uint4*>(win)[q] = x;
-	}
-	__syncthreads();
-	const uint8_t* w = win + shf;
-	r.shf = shf;
-	// 2. N1: the next command's offset for a command starting at x
-	static_assert(kDecWin == 16 * kDecBlock, "16 window offsets per thread");
-	{
-		const uint32_t x0 = 16 * tid;
-		constexpr uint32_t bb = (uint32_t)kNxBad | ((uint32_t)kNxBad << 16);
-		uint4* dst = reinterpret_cast<uint4*>(N1 + x0);
-		dst[0] = make_uint4(bb, bb, bb, bb);
-		dst[1] = make_uint4(bb, bb, bb, bb);
-		uint32_t d[4];
-		win16(w + x0, d);
-		uint32_t cand = 0;
-#pragma unroll
-		for (uint32_t k = 0; k < 16; ++k) cand |= (((d[k >> 2] >> (8 * (k & 3))) & 0xFFu) <= 2u ? 1u : 0u) << k;
-		const uint32_t lim = avail > x0 ? umin32(avail - x0, 16u) : 0u;
-		cand &= (1u << lim) - 1u;
-		for (; cand; cand &= cand - 1) {
-			const uint32_t x = x0 + (uint32_t)__builtin_ctz(cand);
-			const uint32_t t = w[x];
-			uint32_t nx = kNxEnd;
-			if (t != 0) {
-				const uint32_t hdr = t == 1 ? 13u : 9u;
-				if (x + hdr > avail) {
-					nx = pos + x + hdr > dl ? kNxBad : kNxCut;
-				} else {
-					uint32_t lw = 0;
-					__builtin_memcpy(&lw, w + x + 5, 4);
-					const uint64_t len = t == 1 ? 0 : __builtin_bswap32(lw);
-					const uint64_t end = (uint64_t)x + hdr + len;
-					if (pos + end > dl) nx = kNxBad;
-					else nx = end >= avail ? kNxFar : (uint32_t)end;
-				}
-			}
-			N1[x] = (uint16_t)nx;
-		}
-	}
-	__syncthreads();
-	// 3. pointer doubling
-	auto dbl = [&](const uint16_t* src, uint16_t* dstN) {
-		const uint32_t x0 = 16 * tid;
-		const uint4* sp = reinterpret_cast<const uint4*>(src + x0);
-		const uint4 a = sp[0], b = sp[1];
-		const uint32_t in[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-		uint32_t o[8];
-#pragma unroll
-		for (uint32_t k = 0; k < 8; ++k) {
-			const uint32_t y0 = in[k] & 0xFFFFu, y1 = in[k] >> 16;
-			const uint32_t z0 = y0 >= kNxSpecial ? y0 : src[y0];
-			const uint32_t z1 = y1 >= kNxSpecial ? y1 : src[y1];
-			o[k] = z0 | (z1 << 16);
-		}
-		uint4* dp = reinterpret_cast<uint4*>(dstN + x0);
-		dp[0] = make_uint4(o[0], o[1], o[2], o[3]);
-		dp[1] = make_uint4(o[4], o[5], o[6], o[7]);
-	};
-	dbl(N1, N2);
-	__syncthreads();
-	dbl(N2, N4);
-	__syncthreads();
-	dbl(N4, N8);
-	__syncthreads();
-	dbl(N8, N16);
-	__syncthreads();
-	// 4. the walk (wave 0, uniform)
-	if (wave == 0) {
-		uint32_t x = 0, nj = 0, n8 = 0;
-		uint32_t term = 0;
-		while (true) {
-			const uint32_t y = uni(N16[x]);
-			if (y >= kNxSpecial || 16 * (nj + 1) > kDecMaxCmds) break;
-			if (lane == 0) jumps[nj] = (uint16_t)x;
-			++nj;
-			x = y;
-		}
-		uint32_t cnt = 16 * nj;
-		{
-			const uint32_t y = uni(N8[x]);
-			if (y < kNxSpecial && cnt + 8 <= kDecMaxCmds) {
-				if (lane == 0) jumps[nj] = (uint16_t)x;
-				n8 = 1;
-				cnt += 8;
-				x = y;
-			}
-		}
-		while (true) {   // single steps from x (at most 7 commands + the terminal)
-			const uint32_t y = uni(N1[x]);
-			if (y == kNxEnd || y == kNxBad || y == kNxCut) { term = y; break; }
-			if (cnt >= kDecMaxCmds) { term = kNxCut; break; }   // restart the window at x
-			if (lane == 0) cmds[cnt] = (uint16_t)x;
-			++cnt;
-			if (y == kNxFar) { term = kNxFar; break; }
-			x = y;
-		}
-		if (lane == 0) {
-			sh[0] = cnt;
-			sh[1] = nj;
-			sh[2] = x;
-			sh[3] = term;
-			sh[4] = 0;   // a batch out of bounds
-			sh[5] = 0;   // the window is not order-free
-			sh[6] = n8;
-		}
-	}
-	__syncthreads();
-	const uint32_t cnt = sh[0], nj = sh[1], x = sh[2], term = sh[3], n8 = sh[6];
-	for (uint32_t k = tid; k < 2 * nj + n8; k += kDecBlock) {
-		const uint32_t j = k >> 1;
-		const uint32_t e0 = j < nj ? ((k & 1) ? N8[jumps[j]] : jumps[j]) : jumps[nj];
-		const uint32_t e2 = N2[e0];
-		const uint32_t e4 = N2[e2];
-		const uint32_t e6 = N2[e4];
-		uint16_t* c = cmds + (j < nj ? 16 * j + 8 * (k & 1) : 16 * nj);
-		c[0] = (uint16_t)e0;
-		c[1] = N1[e0];
-		c[2] = (uint16_t)e2;
-		c[3] = N1[e2];
-		c[4] = (uint16_t)e4;
-		c[5] = N1[e4];
-		c[6] = (uint16_t)e6;
-		c[7] = N1[e6];
-	}
-	__syncthreads();   // cmds complete; N2..N8 dead
-	r.cnt = cnt;
-	r.next_pos = pos + x;   // kNxCut: restart at x
-	if (term == kNxEnd) r.done = true;
-	else if (term == kNxBad) r.bad = true;
-	else if (term == kNxFar) {
-		const uint32_t t = w[x];
-		r.next_pos = pos + x + (t == 1 ? 13u : 9u + be32(w + x + 5));
-	}
-	// 5. bounds and order checks of every batch (waves in parallel)
-	const uint32_t nb = (cnt + 63) / 64;
-	for (uint32_t b = wave; b < nb; b += kDecWaves) {
-		const DecCmd c = dec_cmd(w, cmds, 64 * b, cnt, pos);
-		bool bad = false;
-		if (c.mine) {
-			if (c.dst + c.len > lim_dst) bad = true;
-			if (c.kind == 1 && c.src + c.len > lim_src) bad = true;
-		}
-		const bool writes = c.mine && c.len != 0 && !(inplace && c.kind == 1 && c.src == c.dst);
-		const uint32_t end32 = writes ? (uint32_t)(c.dst + c.len) : 0u, dst32 = (uint32_t)c.dst;
-		const uint32_t incl_end = wave_incl_max(end32);
-		const bool unordered = writes && dst32 < wave_shr1z(incl_end);
-		const bool moves = c.mine && inplace && c.kind == 1 && c.src != c.dst;
-		const uint64_t wm = __ballot(writes);
-		const uint32_t first_dst = wm ? rdlane(dst32, ffs64(wm)) : ~0u;
-		if (lane == 0) {
-			bsum[2 * b] = first_dst;
-			bsum[2 * b + 1] = rdlane(incl_end, 63);
-		}
-		if (__ballot(bad) && lane == 0) atomicOr(&sh[4], 1u);
-		if (__ballot(unordered || moves) && lane == 0) atomicOr(&sh[5], 1u);
-	}
-	__syncthreads();
-	if (sh[4]) r.bad = true;
-	bool cross = false;   // a batch writes below the end of an earlier batch's writes
-	for (uint32_t b = 0, run = 0; b < nb; ++b) {
-		const uint32_t f = bsum[2 * b], e = bsum[2 * b + 1];
-		if (f != ~0u) {
-			cross = cross || f < run;
-			run = umax32(run, e);
-		}
-	}
-	r.free_win = !sh[5] && !cross;
-	return r;
-}
+static_assert(kUpBlock == kDecBlock, "the window step is written for decode's block");
 
 // CRC-64/XZ of [s0, s0 + len) by the whole block, the value as the header
 // stores it (big-endian u64 of the finalised register), on every thread.
@@ -323,20 +105,6 @@ __device__ uint64_t up_span_crc(const DecCrc& ct, const uint64_t* tables, uintpt
 	return *res;
 }
 
-// The window at pos to LDS (up_window's step 1); returns the offset of its
-// first stream byte in win.
-__device__ __forceinline__ uint32_t up_load_window(uint8_t* win, const uint8_t* D, uint64_t dl, uint64_t pos) {
-	const uintptr_t wa = (uintptr_t)(D + pos) & ~(uintptr_t)15;
-	const uintptr_t dend = (uintptr_t)(D + dl);
-	for (uint32_t q = threadIdx.x; q < (kDecWin + 32) / 16; q += kDecBlock) {
-		const uintptr_t ad = wa + 16 * q;
-		uint4 x = make_uint4(0, 0, 0, 0);
-		if (ad < dend) x = *reinterpret_cast<const uint4*>(ad);
-		reinterpret_cast<uint4*>(win)[q] = x;
-	}
-	return (uint32_t)((uintptr_t)(D + pos) - wa);
-}
-
 // a window's record in the plan's memory: 16 bytes (next_pos, cnt, flags), then cnt u16 offsets, padded to 16
 __device__ __forceinline__ uint64_t up_rec_bytes(uint32_t cnt) { return 16 + ((2ull * cnt + 15) & ~15ull); }
 constexpr uint32_t kUpRecDone = 1, kUpRecFree = 2;
@@ -374,35 +142,7 @@ extern "C" __global__ __launch_bounds__(kUpBlock) __attribute__((amdgpu_waves_pe
 	__shared__ uint64_t cpart[kDecWaves];
 	__shared__ uint32_t clast[kDecWaves];
 	__shared__ uint64_t cres;
-	const UpLds L{win, N1, NX, cmds, jumps, sh, bsum};
-	// the flat copy's per-wave scratch and the grouped apply's arrays, in NX
-	// (dead between the parse and the next window), laid out as in decode_kernel
-	constexpr uint32_t kScratch = 64 * 4 + 128 * 4 + 64 * 8 + 64 * 8 + 64 * 4;
-	static_assert(kDecWaves * kScratch <= 3 * kDecWin * 2, "scratch fits NX");
-	DecScratch xs;
-	{
-		uint8_t* base = reinterpret_cast<uint8_t*>(NX) + wave * kScratch;
-		xs.sp = reinterpret_cast<const uint8_t**>(base);
-		xs.dp = reinterpret_cast<uint8_t**>(base + 64 * 8);
-		xs.cum = reinterpret_cast<uint32_t*>(base + 128 * 8);
-		xs.row = reinterpret_cast<uint32_t*>(base + 128 * 8 + 64 * 4);
-		xs.len = reinterpret_cast<uint32_t*>(base + 128 * 8 + 64 * 4 + 128 * 4);
-	}
-	DecGroupLds grp;
-	{
-		uint8_t* base = reinterpret_cast<uint8_t*>(NX) + kDecWaves * kScratch;
-		grp.src = reinterpret_cast<uint32_t*>(base);
-		grp.dst = grp.src + kDecMaxCmds;
-		grp.len = grp.dst + kDecMaxCmds;
-		grp.pre = grp.len + kDecMaxCmds;                     // kDecMaxCmds + 1 (+3 pad)
-		grp.red = grp.pre + kDecMaxCmds + 4;                 // 8
-		grp.last = reinterpret_cast<int16_t*>(grp.red + 8);  // kDecMaxCmds
-		grp.gs = reinterpret_cast<uint16_t*>(grp.last + kDecMaxCmds);   // kDecMaxCmds + 1 (+1 pad)
-		grp.flag = reinterpret_cast<uint8_t*>(grp.gs + kDecMaxCmds + 2);
-		static_assert(kDecWaves * kScratch + 4 * (4 * kDecMaxCmds + 4 + 8) + 2 * (2 * kDecMaxCmds + 2) + kDecMaxCmds <=
-		                  3 * kDecWin * 2,
-		              "grouped-apply arrays fit NX");
-	}
+	const DecLds L = dec_lds(win, N1, NX, cmds, jumps, sh, bsum);
 
 #ifdef DG_UPDATE_PROF
 	uint64_t uprof[kUpProfN] = {};
@@ -435,7 +175,7 @@ extern "C" __global__ __launch_bounds__(kUpBlock) __attribute__((amdgpu_waves_pe
 	// ── A. validate: nothing is stored before the status is known ──
 	uint64_t vsize = 0;
 	bool inplace = false;
-	if (!st && (dl < 25 || D[0] != 'D' || D[1] != 'L' || D[2] != 'T' || D[3] != 3)) st = 8;
+	if (!st && bad_magic(D, dl)) st = 8;
 	if (!st) {
 		inplace = D[4] & 1;
 		vsize = be32(D + 5);
@@ -451,7 +191,7 @@ extern "C" __global__ __launch_bounds__(kUpBlock) __attribute__((amdgpu_waves_pe
 		bool done = false;
 		while (!done && !st) {
 			if (pos >= dl) break;   // missing END: end of input (as the reference's loop)
-			const UpWin w = up_window(L, D, dl, pos, inplace, lim_dst, lim_src);
+			const DecWin w = dec_window(L, D, dl, pos, inplace, lim_dst, lim_src);
 			if (w.bad) st = 8;
 			if (!st && inplace && cached) {
 				const uint64_t rec = up_rec_bytes(w.cnt);
@@ -524,7 +264,7 @@ extern "C" __global__ __launch_bounds__(kUpBlock) __attribute__((amdgpu_waves_pe
 				cnt = umin32(uni(h.z), kDecMaxCmds);
 				free_win = uni(h.w) & kUpRecFree;
 				next_pos = ((uint64_t)uni(h.y) << 32) | uni(h.x);
-				shf = up_load_window(win, D, dl, pos);
+				shf = dec_load_window(win, D, dl, pos);
 				const uint16_t* q = reinterpret_cast<const uint16_t*>(SC + used + 16);
 				for (uint32_t k = tid; k < cnt; k += kUpBlock) cmds[k] = q[k];
 				__syncthreads();
@@ -532,7 +272,7 @@ extern "C" __global__ __launch_bounds__(kUpBlock) __attribute__((amdgpu_waves_pe
 				++r;
 			} else {
 				if (done || pos >= dl) break;
-				const UpWin w = up_window(L, D, dl, pos, true, bsz, bsz);
+				const DecWin w = dec_window(L, D, dl, pos, true, bsz, bsz);
 				if (w.bad) break;   // (phase A accepted these bytes: not reached)
 				cnt = w.cnt;
 				shf = w.shf;
@@ -547,10 +287,10 @@ extern "C" __global__ __launch_bounds__(kUpBlock) __attribute__((amdgpu_waves_pe
 				const uint32_t nb = (cnt + 63) / 64;
 				for (uint32_t b = wave; b < nb; b += kDecWaves) {
 					const DecCmd c = dec_cmd(wp, cmds, 64 * b, cnt, pos);
-					dec_flat_batch(c, true, O, O, D, xs);
+					dec_flat_batch(c, true, O, O, D, L.xs);
 				}
 			} else {
-				dec_grouped_window(wp, cmds, cnt, pos, true, O, O, D, grp);
+				dec_grouped_window(wp, cmds, cnt, pos, true, O, O, D, L.grp);
 			}
 			block_sync_global();   // the window's stores complete before the next window
 			UPROF_ADD(UP_B_APPLY, tb2);

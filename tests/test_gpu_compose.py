@@ -15,6 +15,7 @@ import random
 import pytest
 
 import compose_cases as cc
+import window_cases as wc
 from stage_timing import check_ring_phases
 
 pytestmark = pytest.mark.gpu
@@ -354,3 +355,14 @@ def test_device_chain_r_to_v2(dg, ctx, orc, torch_cuda):
     fa, fb, fc = oa.cpu().tolist(), ob.cpu().tolist(), oc.cpu().tolist()
     for k in range(n):
         assert hc[fc[k]:fc[k + 1]] == dg.compose(ha[fa[k]:fa[k + 1]], hb[fb[k]:fb[k + 1]]), k
+
+
+# 12. commands cut by, ending at and starting at the end of a parse window
+#     (tests/window_cases.py): each stream as A before an identity B, and as B after an identity A
+def test_parse_window_edges(dg, ctx, orc, torch_cuda):
+    cases = wc.standard_cases(dg, orc)
+    ident_r = cc.identity_delta(dg, orc, cases[0][1])
+    pairs = [(d, cc.identity_delta(dg, orc, V)) for _, _, V, d, _ in cases] + [(ident_r, d) for _, _, _, d, _ in cases]
+    r = Run(torch_cuda, dg, ctx, pairs).run()
+    assert r.status == [OK] * len(pairs)
+    r.check(pairs)

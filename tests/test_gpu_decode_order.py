@@ -16,6 +16,8 @@ import random
 
 import pytest
 
+import window_cases as wc
+
 pytestmark = pytest.mark.gpu
 
 
@@ -174,3 +176,11 @@ def test_inplace_transposition_deltas(dg, ctx, orc, policy):
         rc, Vo = orc.decode(R, d)
         assert rc == 0 and Vo == V
         assert dg.decode(R, d, ctx=ctx) == V, (i, policy)
+
+
+def test_parse_window_edges(dg, ctx, orc):
+    """Commands cut by, ending at and starting at the end of a 1 KiB or 4 KiB
+    parse window, END on either side of it and streams without END
+    (tests/window_cases.py): every stream decodes to its V."""
+    for name, R, V, d, _ in wc.standard_cases(dg, orc) + wc.inplace_cases(dg, orc):
+        assert dg.decode(R, d, ctx=ctx) == V, name

@@ -15,6 +15,8 @@ import random
 
 import pytest
 
+import window_cases as wc
+
 from inplace_graphs import POLICIES, build, named_graphs
 from stage_timing import check_ring_phases
 from test_oracle import inplace_inputs
@@ -340,3 +342,12 @@ def test_stage_times(dg, ctx, orc, torch_cuda):
     st, outs, _, _ = _run(torch_cuda, dg, ctx, items, "localmin", timing=True, after=first_then_phases)
     assert st == [OK] * len(items)
     assert outs == [dg.make_inplace(R, d, "localmin") for R, d in items]
+
+
+# 9. commands cut by, ending at and starting at the end of a parse window (tests/window_cases.py)
+def test_parse_window_edges(dg, ctx, orc, torch_cuda):
+    items = [(R, d) for _, R, _, d, _ in wc.standard_cases(dg, orc)]
+    st, outs, _, _ = _run(torch_cuda, dg, ctx, items, "localmin", odd=True)
+    assert st == [OK] * len(items)
+    for (name, *_), (R, d), got in zip(wc.standard_cases(dg, orc), items, outs):
+        assert got == dg.make_inplace(R, d, "localmin"), name

@@ -19,6 +19,7 @@ import pytest
 
 import compose_cases as cc
 import invert_cases as ic
+import window_cases as wc
 from stage_timing import check_ring_phases
 
 pytestmark = pytest.mark.gpu
@@ -344,3 +345,11 @@ def test_cli_checks_the_reference(dg, orc, tmp_path):
     r = subprocess.run([CLI, "invert", str(pr), str(pa), str(po)], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     assert po.read_bytes() == dg.invert(R, A)
+
+
+# 12. commands cut by, ending at and starting at the end of a parse window (tests/window_cases.py)
+def test_parse_window_edges(dg, ctx, orc, torch_cuda):
+    items = [(R, d) for _, R, _, d, _ in wc.standard_cases(dg, orc)]
+    r = Run(torch_cuda, dg, ctx, items).run()
+    assert r.status == [OK] * len(items)
+    r.check(items)

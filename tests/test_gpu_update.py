@@ -19,6 +19,8 @@ import random
 
 import pytest
 
+import window_cases as wc
+
 from stage_timing import check_ring_phases
 from test_oracle import inplace_inputs
 from update_cases import (DAMAGES, DECODE_AGREES, MOVE_KINDS, ORDER_KINDS, WINDOW, damage, make_delta, moves_case,
@@ -376,3 +378,9 @@ def test_plan_errors_and_surfaces(dg, ctx, orc, torch_cuda, base3):
         dg.update_batch(items, ctx=ctx)
     assert e.value.code == want
     assert dg.update_batch([items[0], items[2]], ctx=ctx) == [good[0][2], V]
+
+
+# commands cut by, ending at and starting at the end of a parse window, in in-place
+# streams built directly (tests/window_cases.py); V is the oracle's replay
+def test_parse_window_edges(dg, ctx, orc, torch_cuda):
+    _apply_all(torch_cuda, dg, ctx, [(R, d, V) for _, R, V, d, _ in wc.inplace_cases(dg, orc)])
