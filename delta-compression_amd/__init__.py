@@ -19,6 +19,10 @@ Names and argument meanings follow the reference's interface for this path:
 * ``invert(R, A)`` / ``InvertPlan`` / ``invert_batch`` — R and delta(R -> V)
   turned into delta(V -> R) without V (no reference counterpart; the normal
   form is stated in ``include/delta_gpu.h``).
+* ``sketch`` / ``SketchPlan`` / ``sketch_batch`` / ``match_sketches`` /
+  ``pick_bases`` — which buffer to encode against: min-wise resemblance
+  sketches over the encoders' fingerprints and base selection by the exact
+  integer rule of ``include/delta_gpu.h`` (no reference counterpart).
 * ``info(delta)``                   — ``delta info`` (main.c:402-425).
 * ``diff`` / ``diff_greedy`` / ``diff_onepass`` / ``diff_correcting``, ``place_commands``,
   ``unplace_commands``, ``encode_delta``, ``decode_delta`` — the command-list
@@ -54,6 +58,13 @@ from ._lib import (  # noqa: F401
     ComposePlan,
     InvertDesc,
     InvertPlan,
+    SketchPlan,
+    SKETCH_BINS,
+    SKETCH_EMPTY,
+    MATCH_NONE,
+    MATCH_ALL,
+    MATCH_NOT_SELF,
+    MATCH_EARLIER,
     LIB_PATH,
     LIMIT_ONEPASS_MEMBERS,
     LIMIT_TABLE_POOL_BYTES,
@@ -82,6 +93,11 @@ from ._lib import (  # noqa: F401
     compose_batch,
     invert,
     invert_batch,
+    sketch,
+    sketch_batch,
+    match_sketches,
+    match_sketches_device,
+    pick_bases,
     output_size,
     place_commands,
     status_string,
@@ -93,6 +109,8 @@ __all__ = [
     "MAX_TABLE_SIZE", "BUF_CAP", "Context", "DeltaError", "DiffOptions", "EncodePlan", "DecodePlan", "InplacePlan", "UpdatePlan",
     "ComposeDesc", "ComposePlan", "compose", "compose_batch",
     "InvertDesc", "InvertPlan", "invert", "invert_batch",
+    "SketchPlan", "sketch", "sketch_batch", "match_sketches", "match_sketches_device", "pick_bases", "SKETCH_BINS", "SKETCH_EMPTY",
+    "MATCH_NONE", "MATCH_ALL", "MATCH_NOT_SELF", "MATCH_EARLIER",
     "crc64_xz", "decode", "default_context", "encode", "encode_batch", "encode_pipelined", "info", "lib",
     "make_inplace", "make_inplace_batch", "update_batch", "status_string", "LIB_PATH", "LIMIT_TABLE_POOL_BYTES",
     "LIMIT_ONEPASS_MEMBERS", "MEMBERS_AUTO", "MEMBERS_ON", "MEMBERS_OFF",

@@ -25,6 +25,11 @@ BUF_CAP = 256
 OPT_VERBOSE, OPT_SPLAY, OPT_INPLACE, OPT_POLICY_CONSTANT = 0, 1, 2, 3
 POLICIES = {"localmin": 0, "constant": 1}
 CMD_COPY, CMD_ADD = 0, 1   # DG_CMD_COPY / DG_CMD_ADD
+SKETCH_BINS = 256
+SKETCH_EMPTY = 0xFFFFFFFFFFFFFFFF
+MATCH_NONE = 0xFFFFFFFF
+MATCH_ALL, MATCH_NOT_SELF, MATCH_EARLIER = 0, 1, 2
+_MATCH_MODES = {"all": MATCH_ALL, "not_self": MATCH_NOT_SELF, "earlier": MATCH_EARLIER}
 
 _ALGOS = {"greedy": ALGO_GREEDY, "onepass": ALGO_ONEPASS, "correcting": ALGO_CORRECTING}
 
@@ -91,6 +96,10 @@ class ComposeDesc(C.Structure):   # dg_compose_desc_t
 class InvertDesc(C.Structure):   # dg_invert_desc_t
     _fields_ = [("ref_off", C.c_uint64), ("ref_len", C.c_uint64),
                 ("delta_off", C.c_uint64), ("delta_cap", C.c_uint64)]
+
+
+class Match(C.Structure):   # dg_match_t
+    _fields_ = [("best", C.c_uint32), ("equal", C.c_uint32), ("used", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class InplaceStats(C.Structure):
@@ -224,6 +233,17 @@ def _load() -> C.CDLL:
         "dg_invert_plan_destroy": (None, [vp]),
         "dg_invert_batch": (C.c_int, [vp, C.POINTER(u8p), C.POINTER(sz), C.POINTER(u8p), C.POINTER(sz), u32,
                                       C.POINTER(Buffer), C.POINTER(i32)]),
+        "dg_sketch": (C.c_int, [u8p, sz, u32, u32, C.POINTER(u64)]),
+        "dg_sketch_match": (C.c_int, [C.POINTER(u64), u32, C.POINTER(u64), u32, u32, C.c_int, u32, u32,
+                                      C.POINTER(Match)]),
+        "dg_sketch_plan_create": (C.c_int, [vp, C.POINTER(Span), u32, u32, u32, C.POINTER(vp)]),
+        "dg_sketch_plan_chunk_bytes": (u32, [vp]),
+        "dg_sketch_plan_run": (C.c_int, [vp, vp, vp, vp]),
+        "dg_sketch_plan_set_timing": (C.c_int, [vp, C.c_int]),
+        "dg_sketch_plan_stage_times": (C.c_int, [vp, C.POINTER(C.c_float), C.POINTER(C.c_char_p), C.c_int]),
+        "dg_sketch_plan_destroy": (None, [vp]),
+        "dg_sketch_match_device": (C.c_int, [vp, vp, u32, vp, u32, u32, C.c_int, u32, u32, vp, vp]),
+        "dg_sketch_batch": (C.c_int, [vp, C.POINTER(u8p), C.POINTER(sz), u32, u32, u32, C.POINTER(u64)]),
         "dg_synth_edit_pairs_device": (C.c_int, [vp, vp, vp, u32, u64, u64, u64, vp]),
         "dg_synth_shift_pairs_device": (C.c_int, [vp, u64, u32, u64, u64, u32, C.POINTER(Pair),
                                                   C.POINTER(u64), C.POINTER(u64), vp, vp, vp]),
@@ -811,6 +831,107 @@ def invert_batch(items: Sequence[Tuple[bytes, bytes]], ctx: Optional[Context] = 
         if st[i]:
             raise DeltaError(st[i], f"delta {i}")
     return res
+
+
+class SketchPlan(_Plan):
+    """dg_sketch_plan_t: the resemblance sketches of a batch of spans of one
+    device arena.  spans: (off, len) per buffer; run writes span i's k words
+    at d_sketch + 8 k i."""
+
+    _prefix = "dg_sketch_plan"
+
+    def __init__(self, ctx: Context, spans: Sequence[Tuple[int, int]], p: int = SEED_LEN, k: int = SKETCH_BINS):
+        self.ctx = ctx
+        n = len(spans)
+        arr = (Span * max(n, 1))(*[Span(*s) for s in spans])
+        h = C.c_void_p()
+        ctx.check(lib.dg_sketch_plan_create(ctx.handle, arr, n, p, k, C.byref(h)), "dg_sketch_plan_create")
+        self._own(h)
+        self.n, self.p, self.k = n, p, k
+
+    @property
+    def chunk_bytes(self) -> int:
+        return lib.dg_sketch_plan_chunk_bytes(self.handle)
+
+    def run(self, d_arena: int, d_sketch: int, stream: int = 0):
+        self.ctx.check(lib.dg_sketch_plan_run(self.handle, d_arena or None, d_sketch or None, stream or None),
+                       "dg_sketch_plan_run")
+
+
+def _match_mode(mode) -> int:
+    if isinstance(mode, str):
+        if mode not in _MATCH_MODES:
+            raise ValueError(f"Unknown match mode: {mode}")
+        return _MATCH_MODES[mode]
+    return int(mode)
+
+
+def sketch(data: bytes, p: int = SEED_LEN, k: int = SKETCH_BINS) -> List[int]:
+    """The resemblance sketch of one buffer (dg_sketch): k words, host only."""
+    out = (C.c_uint64 * max(k, 1))()
+    rc = lib.dg_sketch(_u8(data), len(data), p, k, out)
+    if rc:
+        raise DeltaError(rc, "dg_sketch")
+    return list(out)
+
+
+def sketch_batch(buffers: Sequence[bytes], p: int = SEED_LEN, k: int = SKETCH_BINS,
+                 ctx: Optional[Context] = None) -> List[List[int]]:
+    """The sketches of many buffers, computed on the device in one batch
+    (dg_sketch_batch); equal to sketch buffer by buffer."""
+    ctx = ctx or default_context()
+    n = len(buffers)
+    keep = [bytes(b) for b in buffers]
+    bp = (C.POINTER(C.c_uint8) * max(n, 1))(*[_u8(b) for b in keep])
+    bl = (C.c_size_t * max(n, 1))(*[len(b) for b in keep])
+    out = (C.c_uint64 * max(n * k, 1))()
+    ctx.check(lib.dg_sketch_batch(ctx.handle, bp, bl, n, p, k, out), "dg_sketch_batch")
+    return [list(out[i * k:(i + 1) * k]) for i in range(n)]
+
+
+def match_sketches(targets: Sequence[Sequence[int]], cands: Sequence[Sequence[int]], k: int = SKETCH_BINS,
+                   mode="all", target_base: int = 0, min_equal: int = 1) -> List[Tuple[int, int, int]]:
+    """(best, equal, used) per target sketch among the candidate sketches
+    (dg_sketch_match, host only); best is MATCH_NONE when nothing is eligible."""
+    n_t, n_c = len(targets), len(cands)
+    ta = (C.c_uint64 * max(n_t * k, 1))(*[w for s in targets for w in s])
+    ca = (C.c_uint64 * max(n_c * k, 1))(*[w for s in cands for w in s])
+    out = (Match * max(n_t, 1))()
+    rc = lib.dg_sketch_match(ta, n_t, ca, n_c, k, _match_mode(mode), target_base, min_equal, out)
+    if rc:
+        raise DeltaError(rc, "dg_sketch_match")
+    return [(out[i].best, out[i].equal, out[i].used) for i in range(n_t)]
+
+
+def match_sketches_device(ctx: Context, d_targets: int, n_t: int, d_cands: int, n_c: int, d_out: int,
+                          k: int = SKETCH_BINS, mode="all", target_base: int = 0, min_equal: int = 1, stream: int = 0):
+    """match_sketches on device arrays (dg_sketch_match_device): one launch on
+    the stream; d_out receives n_t dg_match_t (four uint32 each)."""
+    ctx.check(lib.dg_sketch_match_device(ctx.handle, d_targets or None, n_t, d_cands or None, n_c, k, _match_mode(mode),
+                                         target_base, min_equal, d_out or None, stream or None),
+              "dg_sketch_match_device")
+
+
+def pick_bases(buffers: Sequence[bytes], mode="earlier", p: int = SEED_LEN, k: int = SKETCH_BINS,
+               min_equal: int = 1, ctx: Optional[Context] = None) -> List[Tuple[Optional[int], int, int]]:
+    """For every buffer the most resembling other one as its base: (best | None,
+    equal, used).  The sketches and the matching run on the device; in
+    "earlier" mode a base always comes before its buffer, so the assignment has
+    no cycle."""
+    import numpy as np
+    import torch
+    ctx = ctx or default_context()
+    n = len(buffers)
+    if n == 0:
+        return []
+    words = np.array(sketch_batch(buffers, p, k, ctx), dtype=np.uint64).view(np.int64)
+    sk = torch.from_numpy(words).cuda()
+    out = torch.zeros(n * 4, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()   # (torch filled the buffers on its own stream)
+    match_sketches_device(ctx, sk.data_ptr(), n, sk.data_ptr(), n, out.data_ptr(), k, mode, 0, min_equal)
+    torch.cuda.ExternalStream(ctx.stream).synchronize()
+    res = (out.cpu().view(n, 4).to(torch.int64) & 0xFFFFFFFF).tolist()
+    return [(None if b == MATCH_NONE else b, e, u) for b, e, u, _ in res]
 
 
 def update_batch(items: Sequence[Tuple[bytes, bytes]], ignore_hash: bool = False,

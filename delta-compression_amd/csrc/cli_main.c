@@ -12,6 +12,7 @@
  *   delta inplace <ref> <delta_in> <delta_out> [--policy localmin|constant]
  *   delta compose <delta_ab> <delta_bc> <delta_out> [--ignore-hash]
  *   delta invert <ref> <delta_in> <delta_out> [--ignore-hash]
+ *   delta pick [--seed-len P] [--bins K] <version> <candidate>...
  *
  * --inplace / inplace run the CRWI conversion on the host (dg_make_inplace,
  * main.c:279-283 and :427-480).  --splay applies to greedy only (its tie-break
@@ -20,7 +21,10 @@
  * delta(V1 -> V2) into delta(R -> V2) on the host (dg_compose): no GPU and
  * none of R, V1 or V2.  invert turns R and delta(R -> V) into delta(V -> R) on
  * the host (dg_invert) without V; it first checks R's CRC against the delta's
- * (on the GPU, as decode does) unless --ignore-hash is given.
+ * (on the GPU, as decode does) unless --ignore-hash is given.  pick prints the
+ * resemblance score equal/used of the version with every candidate, in argument
+ * order, and the candidate to encode against (dg_sketch, dg_sketch_match: host
+ * only, no GPU).
  */
 #include <errno.h>
 #include <getopt.h>
@@ -97,6 +101,7 @@ static void usage(void)
 	    "  delta inplace <ref> <delta_in> <delta_out> [--policy P]\n"
 	    "  delta compose <delta_ab> <delta_bc> <delta_out> [--ignore-hash]\n"
 	    "  delta invert <ref> <delta_in> <delta_out> [--ignore-hash]\n"
+	    "  delta pick [--seed-len P] [--bins K] <version> <candidate>...\n"
 	    "\n"
 	    "Algorithms: greedy, onepass, correcting (MI355X)\n"
 	    "\n"
@@ -466,6 +471,67 @@ static int cmd_invert(int argc, char **argv)
 	return 0;
 }
 
+/* delta pick [--seed-len P] [--bins K] <version> <candidate>...: which candidate
+ * to encode the version against, by the host functions (no GPU) */
+static int cmd_pick(int argc, char **argv)
+{
+	uint32_t p = DG_SEED_LEN, K = DG_SKETCH_BINS;
+	static struct option lo[] = {
+		{"seed-len", required_argument, NULL, 's'},
+		{"bins", required_argument, NULL, 'b'},
+		{NULL, 0, NULL, 0}};
+	optind = 2;
+	int opt;
+	while ((opt = getopt_long(argc, argv, "", lo, NULL)) != -1) {
+		if (opt != 's' && opt != 'b') usage();
+		char *end = NULL;
+		unsigned long v = strtoul(optarg, &end, 10);
+		if (!*optarg || *end || v > 0xFFFFFFFFul) {
+			fprintf(stderr, "delta_pick: bad option value: %s\n", optarg);
+			return 1;
+		}
+		if (opt == 's') p = (uint32_t)v;
+		else K = (uint32_t)v;
+	}
+	if (argc - optind < 2) usage();
+	const int n = argc - optind - 1;   /* candidates */
+	if (p < 1 || p > 64 || K < 16 || K > 1024 || (K & (K - 1))) {
+		fprintf(stderr, "delta_pick: --seed-len must be 1..64 and --bins a power of two in 16..1024\n");
+		return 1;
+	}
+	uint64_t *sk = malloc((size_t)(n + 1) * K * sizeof *sk);
+	dg_match_t one;
+	if (!sk) {
+		fprintf(stderr, "delta_pick: out of memory\n");
+		return 1;
+	}
+	for (int i = 0; i <= n; i++) {   /* sketch 0: the version */
+		size_t len;
+		uint8_t *d = read_file(argv[optind + i], &len);
+		int rc = dg_sketch(d, len, p, K, sk + (size_t)i * K);
+		free(d);
+		if (rc) {
+			fprintf(stderr, "delta_pick: %s: %s\n", argv[optind + i], dg_status_string(rc));
+			return 1;
+		}
+	}
+	for (int i = 1; i <= n; i++) {
+		dg_sketch_match(sk, 1, sk + (size_t)i * K, 1, K, DG_MATCH_ALL, 0, 1, &one);
+		if (one.best == DG_MATCH_NONE) {   /* below min_equal: report the plain counts */
+			uint32_t used = 0;
+			for (uint32_t b = 0; b < K; b++)
+				used += sk[b] != DG_SKETCH_EMPTY || sk[(size_t)i * K + b] != DG_SKETCH_EMPTY;
+			one.equal = 0, one.used = used;
+		}
+		printf("%u/%u\t%s\n", one.equal, one.used, argv[optind + i]);
+	}
+	dg_sketch_match(sk, 1, sk + K, (uint32_t)n, K, DG_MATCH_ALL, 0, 1, &one);
+	if (one.best == DG_MATCH_NONE) printf("best: none\n");
+	else printf("best: %s\n", argv[optind + 1 + one.best]);
+	free(sk);
+	return 0;
+}
+
 int main(int argc, char **argv)
 {
 	if (argc < 2) usage();
@@ -475,6 +541,7 @@ int main(int argc, char **argv)
 	if (strcmp(argv[1], "inplace") == 0) return cmd_inplace(argc, argv);
 	if (strcmp(argv[1], "compose") == 0) return cmd_compose(argc, argv);
 	if (strcmp(argv[1], "invert") == 0) return cmd_invert(argc, argv);
+	if (strcmp(argv[1], "pick") == 0) return cmd_pick(argc, argv);
 	usage();
 	return 1;
 }

@@ -44,29 +44,8 @@ constexpr uint32_t kBuildSeedsPerBlock = kBuildSeedsPerLane * kBuildBlock;   // 
 
 __device__ __forceinline__ uint32_t umin_(uint32_t a, uint32_t b) { return a < b ? a : b; }
 
-__device__ __forceinline__ uint64_t fold61c(uint64_t lo, uint64_t hi) {
-	// lo + hi * 2^32 mod (2^61 - 1), lo < 2^48, hi < 2^45
-	return mod_m61(lo + ((hi & ((1ULL << 29) - 1)) << 32) + (hi >> 29));
-}
-
-// One rolling step (hash.c:62-98) fp' = (fp - out 263^(p-1)) 263 + in
-// = fp 263 + nb + in (mod M), with nb = -out 263^p mod M from a table
-// (roll_table): with fp = h 2^32 + l (h < 2^29),
-//   fp 263 + nb + in = (l 263 + nb_lo + in) + (h 263 + nb_hi) 2^32
-// and (h 263 + nb_hi) 2^32 == (.. >> 29) + (.. & (2^29-1)) 2^32, so the sum
-// is < 2^62 and one fold plus one subtract make it canonical.  Two 32x32
-// multiply-adds instead of the subtract-fold-multiply-fold of the textbook
-// form.  fp must be canonical (< M); so is the result.
-__device__ __forceinline__ uint64_t roll61(uint64_t fp, uint64_t nb, uint32_t in) {
-	const uint64_t plo = (uint64_t)(uint32_t)fp * (uint32_t)kBase + (uint32_t)nb + in;   // < 2^42
-	const uint64_t phi = (uint64_t)(uint32_t)(fp >> 32) * (uint32_t)kBase + (nb >> 32);  // < 2^39
-	const uint64_t t = plo + ((phi & ((1ULL << 29) - 1)) << 32) + (phi >> 29);           // < 2^61 + 2^43
-	const uint64_t r = (t & kMersenne) + (t >> 61);
-	return r >= kMersenne ? r - kMersenne : r;
-}
-
-// The same step on a weakly reduced fingerprint (any value <= M + 2 with
-// the high dword <= 2^29, i.e. the residue plus 0..2 M), for the build's
+// The rolling step (roll61, dg_devutil.h) on a weakly reduced fingerprint
+// (any value <= M + 2 with the high dword <= 2^29, i.e. the residue plus 0..2 M), for the build's
 // unrolled seed loop.  With fp = h 2^32 + l:
 //   P = l 263 + nb (one 32x32+64 multiply-add, nb straight from the table),
 //   Q = h 263 < 2^39, and Q 2^32 == (Q & (2^29-1)) 2^32 + (Q >> 29),
@@ -93,17 +72,6 @@ __device__ __forceinline__ uint64_t fp61_canon(uint64_t r) {
 	const uint32_t lo = (uint32_t)r + (ge ? 1u : 0u);
 	const uint32_t hi = ge ? 0u : (uint32_t)(r >> 32);
 	return ((uint64_t)hi << 32) | lo;
-}
-
-// x * c mod M for x < 2^61 and c < 2^32
-__device__ __forceinline__ uint64_t mulsmall61(uint64_t x, uint32_t c) {
-	return fold61c((x & 0xFFFFFFFFull) * c, (x >> 32) * c);
-}
-
-// the roll61 table entry of byte x: -x 263^p mod M (c = 263^(p-1) mod M)
-__device__ __forceinline__ uint64_t roll_table(uint32_t x, uint64_t c) {
-	const uint64_t v = mulsmall61(mulsmall61(c, (uint32_t)kBase), x);   // x 263^p
-	return v ? kMersenne - v : 0;
 }
 
 // checkpoint class k: fingerprint of V[|V|/2 .. +p) (correcting.c:131-136),

@@ -147,6 +147,38 @@ __device__ __forceinline__ uint64_t window_fp(const uint8_t* d, uint32_t p,
 	return mod_m61(t);
 }
 
+__device__ __forceinline__ uint64_t fold61c(uint64_t lo, uint64_t hi) {
+	// lo + hi * 2^32 mod (2^61 - 1), lo < 2^48, hi < 2^45
+	return mod_m61(lo + ((hi & ((1ULL << 29) - 1)) << 32) + (hi >> 29));
+}
+
+// One rolling step (hash.c:62-98) fp' = (fp - out 263^(p-1)) 263 + in
+// = fp 263 + nb + in (mod M), with nb = -out 263^p mod M from a table
+// (roll_table): with fp = h 2^32 + l (h < 2^29),
+//   fp 263 + nb + in = (l 263 + nb_lo + in) + (h 263 + nb_hi) 2^32
+// and (h 263 + nb_hi) 2^32 == (.. >> 29) + (.. & (2^29-1)) 2^32, so the sum
+// is < 2^62 and one fold plus one subtract make it canonical.  Two 32x32
+// multiply-adds instead of the subtract-fold-multiply-fold of the textbook
+// form.  fp must be canonical (< M); so is the result.
+__device__ __forceinline__ uint64_t roll61(uint64_t fp, uint64_t nb, uint32_t in) {
+	const uint64_t plo = (uint64_t)(uint32_t)fp * (uint32_t)kBase + (uint32_t)nb + in;   // < 2^42
+	const uint64_t phi = (uint64_t)(uint32_t)(fp >> 32) * (uint32_t)kBase + (nb >> 32);  // < 2^39
+	const uint64_t t = plo + ((phi & ((1ULL << 29) - 1)) << 32) + (phi >> 29);           // < 2^61 + 2^43
+	const uint64_t r = (t & kMersenne) + (t >> 61);
+	return r >= kMersenne ? r - kMersenne : r;
+}
+
+// x * c mod M for x < 2^61 and c < 2^32
+__device__ __forceinline__ uint64_t mulsmall61(uint64_t x, uint32_t c) {
+	return fold61c((x & 0xFFFFFFFFull) * c, (x >> 32) * c);
+}
+
+// the roll61 table entry of byte x: -x 263^p mod M (c = 263^(p-1) mod M)
+__device__ __forceinline__ uint64_t roll_table(uint32_t x, uint64_t c) {
+	const uint64_t v = mulsmall61(mulsmall61(c, (uint32_t)kBase), x);   // x 263^p
+	return v ? kMersenne - v : 0;
+}
+
 // The correcting checkpoint test (correcting.c:164-198): f = fp mod |F|
 // passes iff f mod m == k, and its slot is f / m (< cap).  FP64 path for
 // |F| < 2^23: mod_q_small, then one floor-quotient by m fixed up by one.

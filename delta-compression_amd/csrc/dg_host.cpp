@@ -47,7 +47,7 @@ struct dg_context {
 	// code objects loaded at run time: the in-place conversion module
 	// (dg_inplace_host.cpp), the in-place update module (dg_update_host.cpp),
 	// the composition module (dg_compose_host.cpp), the inversion module
-	// (dg_invert_host.cpp)
+	// (dg_invert_host.cpp), the sketch module (dg_sketch_host.cpp)
 	void* module[kCtxModules] = {};
 	void (*module_free[kCtxModules])(void*) = {};
 };

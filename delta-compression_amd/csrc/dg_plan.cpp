@@ -678,6 +678,42 @@ int invert_plan_geometry_for(const EncodePlanView& e, uint32_t n, InvertGeometry
 	return invert_finish(g, err);
 }
 
+// ── sketch plan: the (span, chunk) work list ──
+
+int sketch_plan_geometry(const dg_span_t* spans, uint32_t n, uint32_t p, uint32_t K, uint32_t chunk_bytes,
+                         SketchGeometry& g, std::string& err) {
+	using namespace dgsk;
+	if (p < 1 || p > kMaxSeed) return fail(err, DG_ERR_INVALID_ARG, "sketch plan: seed length %u is not in 1..%u", p, kMaxSeed);
+	if (K < kMinBins || K > kMaxBins || (K & (K - 1)))
+		return fail(err, DG_ERR_INVALID_ARG, "sketch plan: %u bins is not a power of two in %u..%u", K, kMinBins, kMaxBins);
+	if (!chunk_bytes) chunk_bytes = kChunkBytes;
+	if (chunk_bytes % (4 * kSkBlock) || chunk_bytes > 16384)
+		return fail(err, DG_ERR_INVALID_ARG, "sketch plan: a chunk of %u bytes is not a multiple of %u up to 16384", chunk_bytes,
+		            4 * kSkBlock);
+	g.chunk_bytes = chunk_bytes;
+	g.shift = 64 - (uint32_t)__builtin_ctz(K);
+	g.powc.resize(p);
+	uint64_t c = 1;
+	for (uint32_t k = 0; k < p; ++k) {
+		g.powc[p - 1 - k] = c;
+		c = (uint64_t)((u128)c * kBase % kMersenne);
+	}
+	g.items.clear();
+	for (uint32_t i = 0; i < n; ++i) {
+		if (spans[i].len >= (1ull << 32))
+			return fail(err, DG_ERR_TOO_LARGE, "sketch plan: span %u: 4 GiB or more", i);
+		if (spans[i].off + spans[i].len < spans[i].off)
+			return fail(err, DG_ERR_INVALID_ARG, "sketch plan: span %u wraps the address space", i);
+		if (spans[i].len < p) continue;
+		const uint64_t windows = spans[i].len - p + 1;
+		const uint64_t chunks = (windows + chunk_bytes - 1) / chunk_bytes;
+		if (g.items.size() + chunks > 0x7FFFFFFFull)
+			return fail(err, DG_ERR_TOO_LARGE, "sketch plan: more than 2^31 - 1 chunks");
+		for (uint32_t k = 0; k < chunks; ++k) g.items.push_back(SkItem{i, k});
+	}
+	return DG_OK;
+}
+
 // ── update plan: descriptor checks ──
 
 int update_check_descs(const dg_update_desc_t* descs, uint32_t n, std::string& err) {

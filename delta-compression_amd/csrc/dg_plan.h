@@ -13,6 +13,7 @@
 #include "dg_inplace_dev.h"
 #include "dg_invert_dev.h"
 #include "dg_layout.h"
+#include "dg_sketch_dev.h"
 
 namespace dg {
 
@@ -137,6 +138,21 @@ struct InvertGeometry {
 uint32_t invert_max_copies(uint64_t cap);
 int invert_plan_geometry(const dg_invert_desc_t* descs, uint32_t n, InvertGeometry& g, std::string& err);
 int invert_plan_geometry_for(const EncodePlanView& e, uint32_t n, InvertGeometry& g, std::string& err);
+
+// ── the sketch plan (dg_sketch_host.cpp) ──
+struct SketchGeometry {
+	std::vector<dgsk::SkItem> items;   // the grid: one block per (span, chunk), span by span
+	std::vector<uint64_t> powc;        // 263^(p-1-k) mod (2^61-1); powc[0] is SkArgs::top
+	uint32_t chunk_bytes = 0;          // window starts per chunk (dg_sketch_plan_chunk_bytes)
+	uint32_t shift = 0;                // 64 - log2 K
+};
+// Validates p, K and the spans (DG_ERR_INVALID_ARG; DG_ERR_TOO_LARGE for a span
+// of 4 GiB or more, or more chunks than a grid holds) and cuts every span's
+// n - p + 1 windows into chunks of chunk_bytes window starts (0: the default,
+// dgsk::kChunkBytes).  A chunk's windows are those starting in it; the last
+// p - 1 of them read into the next chunk, none past the span.
+int sketch_plan_geometry(const dg_span_t* spans, uint32_t n, uint32_t p, uint32_t K, uint32_t chunk_bytes,
+                         SketchGeometry& g, std::string& err);
 
 // dg_update_plan_create's descriptor checks: DG_OK, DG_ERR_TOO_LARGE (a buffer
 // or a length of 4 GiB or more) or DG_ERR_INVALID_ARG (a region wrapping the

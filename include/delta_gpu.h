@@ -916,6 +916,134 @@ int dg_invert_batch(dg_context_t *ctx, const uint8_t *const *r, const size_t *r_
                     const uint8_t *const *delta, const size_t *delta_len, uint32_t n,
                     dg_buffer_t *outs, int32_t *status);
 
+/* ── reference selection: resemblance sketches and base matching ─────────────
+ *
+ * Every entry point above starts from a pair: the caller knows which R a V is
+ * encoded against.  A store that receives a new object has to choose that R
+ * among the buffers it holds, and a poor choice costs more than any encoder
+ * wins back: a delta against an unrelated buffer is |V| plus framing.  The
+ * choice is resemblance detection by min-wise sketches (Broder) over the
+ * fingerprints the encoders already compute, in the one-permutation form: one
+ * hash per window, K bins, the minimum of each bin.  (The reference has no
+ * such step.)  The result feeds dg_encode_plan_create: target t against
+ * candidate best[t] is one dg_pair_t.
+ *
+ * Sketch.  Parameters: the seed length p, 1 <= p <= 64 (DG_SEED_LEN is the
+ * default), and the bin count K, a power of two with 16 <= K <= 1024
+ * (DG_SKETCH_BINS is the default).  For a buffer X of n bytes:
+ *   features  fp_a = the Karp-Rabin fingerprint of X[a .. a + p) for every
+ *             byte offset a = 0 .. n - p: Horner with base 263 mod 2^61 - 1
+ *             (hash.c:28-38).  Every offset counts, so the feature set does
+ *             not move when bytes are inserted in front;
+ *   hash      h_a = mix(fp_a), the splitmix64 finaliser, mod 2^64:
+ *               z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9
+ *               z = (z ^ (z >> 27)) * 0x94D049BB133111EB
+ *               z ^= z >> 31
+ *   bin       bin(h) = h >> (64 - log2 K);
+ *   sketch    sketch[b] = the minimum h_a over the features with bin(h_a) = b;
+ *             a bin no feature falls into holds DG_SKETCH_EMPTY; when n < p
+ *             every bin does.
+ * A sketch is K uint64_t in bin order (2 KiB at the default K) and a pure
+ * function of (bytes, p, K).  The definition is frozen: stores persist
+ * sketches.  The host function, the device path and the tests' Python model
+ * produce it bit for bit.
+ *
+ * Score.  For two sketches A and B of the same (p, K):
+ *   equal = #{b : A[b] == B[b] != DG_SKETCH_EMPTY}
+ *   used  = #{b : A[b] != DG_SKETCH_EMPTY or B[b] != DG_SKETCH_EMPTY}
+ * and equal / used estimates the Jaccard resemblance of the two fingerprint
+ * sets.  Scores are compared as exact rationals by cross-multiplication (both
+ * numbers are at most 1024); no floating point appears anywhere.
+ *
+ * Selection.  Target t of n_t (a window of a larger set: its index in that set
+ * is target_base + t) against candidates c = 0 .. n_c - 1.  c is admissible
+ *   DG_MATCH_ALL       always;
+ *   DG_MATCH_NOT_SELF  when c != target_base + t;
+ *   DG_MATCH_EARLIER   when c < target_base + t: one set matched against
+ *                      itself this way has an acyclic base assignment;
+ * and eligible when also equal_c >= min_equal (min_equal >= 1).  c beats c'
+ * iff equal_c used_c' > equal_c' used_c, or the two products are equal and
+ * c < c'.  The result is the eligible candidate that beats every other:
+ * best, its equal and used, and reserved = 0; with nothing eligible best =
+ * DG_MATCH_NONE and equal = used = 0.
+ *
+ * dg_sketch and dg_sketch_match are pure host code (no context, no GPU);
+ * dg_sketch is linear in len.  A p, K or mode outside the above, or min_equal
+ * == 0, is DG_ERR_INVALID_ARG; a len of 4 GiB or more is DG_ERR_TOO_LARGE. */
+#define DG_SKETCH_BINS  256
+#define DG_SKETCH_EMPTY 0xFFFFFFFFFFFFFFFFull
+#define DG_MATCH_NONE   0xFFFFFFFFu
+#define DG_MATCH_ALL      0
+#define DG_MATCH_NOT_SELF 1
+#define DG_MATCH_EARLIER  2
+typedef struct {
+	uint32_t best;       /* candidate index, or DG_MATCH_NONE */
+	uint32_t equal, used;
+	uint32_t reserved;   /* 0 */
+} dg_match_t;
+
+int dg_sketch(const uint8_t *data, size_t len, uint32_t p, uint32_t K,
+              uint64_t *out /* K words */);
+int dg_sketch_match(const uint64_t *targets /* n_t x K */, uint32_t n_t,
+                    const uint64_t *cands /* n_c x K */, uint32_t n_c, uint32_t K,
+                    int mode, uint32_t target_base, uint32_t min_equal,
+                    dg_match_t *out /* n_t */);
+
+/* ── sketches of a batch and base matching on the device ───────────────────
+ *
+ * The same words, bit for bit.  A sketch plan fixes N spans of one device
+ * arena, p and K; dg_sketch_plan_run writes span i's sketch to
+ * d_sketch[i K .. (i + 1) K).  Every span's windows are cut into chunks of
+ * dg_sketch_plan_chunk_bytes consecutive window starts (one value per plan);
+ * one block takes one chunk: it stages the chunk's bytes and the p - 1 after
+ * them in LDS, every lane fingerprints consecutive windows by rolling, the
+ * block keeps the K bins in LDS and folds its non-empty bins into d_sketch
+ * with 64-bit unsigned-minimum atomics.  A minimum does not depend on the
+ * order, so the result does not depend on the schedule.
+ *
+ * A run first sets all n K words to DG_SKETCH_EMPTY on the stream, so a plan
+ * is run any number of times, on other bytes of the same layout each time, and
+ * no run keeps a minimum of the runs before it.  It is a fill and one kernel
+ * on one stream: no allocation, no host synchronisation.  d_arena is 16-byte
+ * aligned; span offsets and lengths are arbitrary (a span of 4 GiB or more is
+ * DG_ERR_TOO_LARGE); spans may overlap; n == 0 is a valid plan whose run
+ * touches nothing.  No byte outside a span is read and no word outside the
+ * n K outputs is written.
+ *
+ * dg_sketch_match_device is dg_sketch_match on device arrays: stateless, one
+ * kernel launch on the stream.  A wave holds two target sketches in registers
+ * (one from 512 bins up) and streams every candidate sketch past them (compare,
+ * ballot, population count), so the cost is O(n_t n_c K) word comparisons;
+ * d_out needs no alignment beyond a uint32_t's; candidate sketches for
+ * thousands of buffers stay in the last-level cache.  n_t == 0 enqueues
+ * nothing.
+ *
+ * The kernels live in dg_sketch.hsaco beside libdeltagpu.so and are loaded on
+ * first use; DG_ERR_HIP with the path in dg_last_error when it is missing.
+ * Stage timing as for the decode plan: "sketch" (the fill and the kernel) and
+ * "total". */
+typedef struct dg_sketch_plan dg_sketch_plan_t;
+
+int dg_sketch_plan_create(dg_context_t *ctx, const dg_span_t *spans /* host */,
+                          uint32_t n, uint32_t p, uint32_t K, dg_sketch_plan_t **out);
+uint32_t dg_sketch_plan_chunk_bytes(const dg_sketch_plan_t *plan);
+int dg_sketch_plan_run(dg_sketch_plan_t *plan, const uint8_t *d_arena,
+                       uint64_t *d_sketch /* n x K */, void *stream);
+int dg_sketch_plan_set_timing(dg_sketch_plan_t *plan, int slots);
+int dg_sketch_plan_stage_times(dg_sketch_plan_t *plan, float *ms,
+                               const char **names, int n);
+void dg_sketch_plan_destroy(dg_sketch_plan_t *plan);
+
+int dg_sketch_match_device(dg_context_t *ctx, const uint64_t *d_targets, uint32_t n_t,
+                           const uint64_t *d_cands, uint32_t n_c, uint32_t K,
+                           int mode, uint32_t target_base, uint32_t min_equal,
+                           dg_match_t *d_out, void *stream);
+
+/* Host buffers in, sketches out (out: n x K words of host memory), sketched on
+ * the device in one batch; equal to dg_sketch buffer by buffer. */
+int dg_sketch_batch(dg_context_t *ctx, const uint8_t *const *bufs, const size_t *lens,
+                    uint32_t n, uint32_t p, uint32_t K, uint64_t *out);
+
 /* ── synthetic batch generators (bench / test inputs, on the device) ─────
  * Workload definitions in DESIGN.md ("Synthetic inputs"); the oracle's
  * or_synth_* functions produce the same bytes on the CPU. */
