@@ -19,6 +19,10 @@ Names and argument meanings follow the reference's interface for this path:
 * ``invert(R, A)`` / ``InvertPlan`` / ``invert_batch`` — R and delta(R -> V)
   turned into delta(V -> R) without V (no reference counterpart; the normal
   form is stated in ``include/delta_gpu.h``).
+* ``read_range(R, delta, off, length)`` / ``ReadPlan`` / ``read_ranges`` — bytes
+  [off, off + length) of the version a standard delta makes of R, without
+  rebuilding the version (no reference counterpart: the replay of
+  apply.c:229-249, sliced).
 * ``sketch`` / ``SketchPlan`` / ``sketch_batch`` / ``match_sketches`` /
   ``pick_bases`` — which buffer to encode against: min-wise resemblance
   sketches over the encoders' fingerprints and base selection by the exact
@@ -58,6 +62,9 @@ from ._lib import (  # noqa: F401
     ComposePlan,
     InvertDesc,
     InvertPlan,
+    ReadPlan,
+    ReadReq,
+    ReadStream,
     SketchPlan,
     SKETCH_BINS,
     SKETCH_EMPTY,
@@ -93,6 +100,8 @@ from ._lib import (  # noqa: F401
     compose_batch,
     invert,
     invert_batch,
+    read_range,
+    read_ranges,
     sketch,
     sketch_batch,
     match_sketches,
@@ -109,6 +118,7 @@ __all__ = [
     "MAX_TABLE_SIZE", "BUF_CAP", "Context", "DeltaError", "DiffOptions", "EncodePlan", "DecodePlan", "InplacePlan", "UpdatePlan",
     "ComposeDesc", "ComposePlan", "compose", "compose_batch",
     "InvertDesc", "InvertPlan", "invert", "invert_batch",
+    "ReadPlan", "ReadReq", "ReadStream", "read_range", "read_ranges",
     "SketchPlan", "sketch", "sketch_batch", "match_sketches", "match_sketches_device", "pick_bases", "SKETCH_BINS", "SKETCH_EMPTY",
     "MATCH_NONE", "MATCH_ALL", "MATCH_NOT_SELF", "MATCH_EARLIER",
     "crc64_xz", "decode", "default_context", "encode", "encode_batch", "encode_pipelined", "info", "lib",

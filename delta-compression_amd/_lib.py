@@ -98,6 +98,16 @@ class InvertDesc(C.Structure):   # dg_invert_desc_t
                 ("delta_off", C.c_uint64), ("delta_cap", C.c_uint64)]
 
 
+class ReadStream(C.Structure):   # dg_read_stream_t
+    _fields_ = [("ref_off", C.c_uint64), ("ref_len", C.c_uint64),
+                ("delta_off", C.c_uint64), ("delta_len", C.c_uint64)]
+
+
+class ReadReq(C.Structure):   # dg_read_req_t
+    _fields_ = [("stream", C.c_uint32), ("off", C.c_uint32), ("len", C.c_uint32), ("reserved", C.c_uint32),
+                ("out_off", C.c_uint64)]
+
+
 class Match(C.Structure):   # dg_match_t
     _fields_ = [("best", C.c_uint32), ("equal", C.c_uint32), ("used", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -233,6 +243,15 @@ def _load() -> C.CDLL:
         "dg_invert_plan_destroy": (None, [vp]),
         "dg_invert_batch": (C.c_int, [vp, C.POINTER(u8p), C.POINTER(sz), C.POINTER(u8p), C.POINTER(sz), u32,
                                       C.POINTER(Buffer), C.POINTER(i32)]),
+        "dg_read": (C.c_int, [u8p, sz, u8p, sz, u64, u64, C.POINTER(Buffer)]),
+        "dg_read_plan_create": (C.c_int, [vp, C.POINTER(ReadStream), u32, u32, C.POINTER(vp)]),
+        "dg_read_plan_index": (C.c_int, [vp, vp, vp, vp, vp, vp]),
+        "dg_read_plan_run": (C.c_int, [vp, vp, vp, vp, u32, vp, vp, vp, vp]),
+        "dg_read_plan_set_timing": (C.c_int, [vp, C.c_int]),
+        "dg_read_plan_stage_times": (C.c_int, [vp, C.POINTER(C.c_float), C.POINTER(C.c_char_p), C.c_int]),
+        "dg_read_plan_destroy": (None, [vp]),
+        "dg_read_batch": (C.c_int, [vp, C.POINTER(u8p), C.POINTER(sz), C.POINTER(u8p), C.POINTER(sz), u32,
+                                    C.POINTER(ReadReq), u32, C.POINTER(Buffer), C.POINTER(i32)]),
         "dg_sketch": (C.c_int, [u8p, sz, u32, u32, C.POINTER(u64)]),
         "dg_sketch_match": (C.c_int, [C.POINTER(u64), u32, C.POINTER(u64), u32, u32, C.c_int, u32, u32,
                                       C.POINTER(Match)]),
@@ -830,6 +849,81 @@ def invert_batch(items: Sequence[Tuple[bytes, bytes]], ctx: Optional[Context] = 
     for i in range(n):
         if st[i]:
             raise DeltaError(st[i], f"delta {i}")
+    return res
+
+
+class ReadPlan(_Plan):
+    """dg_read_plan_t: byte ranges of versions kept as R plus a standard delta,
+    read on the device without rebuilding the versions.  streams: (ref_off,
+    ref_len, delta_off, delta_len) per stream.  index() parses every stream
+    once (again whenever the delta bytes change); run() serves a device array
+    of ReadReq, one block per request."""
+
+    _prefix = "dg_read_plan"
+
+    def __init__(self, ctx: Context, streams: Sequence[Tuple[int, int, int, int]], max_requests: int):
+        self.ctx = ctx
+        n = len(streams)
+        arr = (ReadStream * max(n, 1))(*[ReadStream(*s) for s in streams])
+        h = C.c_void_p()
+        ctx.check(lib.dg_read_plan_create(ctx.handle, arr, n, int(max_requests), C.byref(h)), "dg_read_plan_create")
+        self._own(h)
+        self.n = n
+        self.max_requests = int(max_requests)
+
+    def index(self, d_delta: int, d_stream_status: int = 0, d_delta_offsets: int = 0, d_delta_status: int = 0,
+              stream: int = 0):
+        self.ctx.check(lib.dg_read_plan_index(self.handle, d_delta, d_delta_offsets or None, d_delta_status or None,
+                                              d_stream_status or None, stream or None), "dg_read_plan_index")
+
+    def run(self, d_ref: int, d_delta: int, d_reqs: int, n_req: int, d_out: int, d_out_len: int, d_status: int,
+            stream: int = 0):
+        self.ctx.check(lib.dg_read_plan_run(self.handle, d_ref or None, d_delta or None, d_reqs or None, int(n_req),
+                                            d_out or None, d_out_len or None, d_status or None, stream or None),
+                       "dg_read_plan_run")
+
+
+def read_range(R: bytes, delta: bytes, off: int, length: int) -> bytes:
+    """Bytes [off, off + length) of the version delta makes of R, clipped to the
+    version (dg_read): host only, no CRC check."""
+    out = Buffer()
+    rc = lib.dg_read(_u8(R), len(R), _u8(delta), len(delta), int(off), int(length), C.byref(out))
+    if rc:
+        raise DeltaError(rc, "dg_read")
+    res = C.string_at(out.data, out.len) if out.len else b""
+    lib.dg_buffer_free(C.byref(out))
+    return res
+
+
+def read_ranges(items: Sequence[Tuple[bytes, bytes]], requests: Sequence[Tuple[int, int, int]],
+                ctx: Optional[Context] = None, status: bool = False):
+    """requests (stream, off, length) read from the (R, delta) items on the
+    device in one batch (dg_read_batch); equal to read_range request by
+    request.  Raises DeltaError for the first failing request; with
+    status=True returns (results, statuses) instead, a failed request's result
+    being b""."""
+    ctx = ctx or default_context()
+    n, m = len(items), len(requests)
+    if m == 0:
+        return ([], []) if status else []
+    keep = [(bytes(r), bytes(d)) for r, d in items]
+    rp = (C.POINTER(C.c_uint8) * max(n, 1))(*[_u8(r) for r, _ in keep])
+    dp = (C.POINTER(C.c_uint8) * max(n, 1))(*[_u8(d) for _, d in keep])
+    rl = (C.c_size_t * max(n, 1))(*[len(r) for r, _ in keep])
+    dl = (C.c_size_t * max(n, 1))(*[len(d) for _, d in keep])
+    rq = (ReadReq * m)(*[ReadReq(int(s), int(o), int(ln), 0, 0) for s, o, ln in requests])
+    outs = (Buffer * m)()
+    st = (C.c_int32 * m)()
+    ctx.check(lib.dg_read_batch(ctx.handle, rp, rl, dp, dl, n, rq, m, outs, st), "dg_read_batch")
+    res = []
+    for j in range(m):
+        res.append(C.string_at(outs[j].data, outs[j].len) if outs[j].len else b"")
+        lib.dg_buffer_free(C.byref(outs[j]))
+    if status:
+        return res, list(st)
+    for j in range(m):
+        if st[j]:
+            raise DeltaError(st[j], f"request {j}")
     return res
 
 

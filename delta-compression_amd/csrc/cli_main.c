@@ -13,6 +13,7 @@
  *   delta compose <delta_ab> <delta_bc> <delta_out> [--ignore-hash]
  *   delta invert <ref> <delta_in> <delta_out> [--ignore-hash]
  *   delta pick [--seed-len P] [--bins K] <version> <candidate>...
+ *   delta read <ref> <delta> <offset> <length> <output>
  *
  * --inplace / inplace run the CRWI conversion on the host (dg_make_inplace,
  * main.c:279-283 and :427-480).  --splay applies to greedy only (its tie-break
@@ -102,6 +103,7 @@ static void usage(void)
 	    "  delta compose <delta_ab> <delta_bc> <delta_out> [--ignore-hash]\n"
 	    "  delta invert <ref> <delta_in> <delta_out> [--ignore-hash]\n"
 	    "  delta pick [--seed-len P] [--bins K] <version> <candidate>...\n"
+	    "  delta read <ref> <delta> <offset> <length> <output>\n"
 	    "\n"
 	    "Algorithms: greedy, onepass, correcting (MI355X)\n"
 	    "\n"
@@ -471,6 +473,34 @@ static int cmd_invert(int argc, char **argv)
 	return 0;
 }
 
+/* delta read <ref> <delta> <offset> <length> <output>: bytes [offset, offset +
+ * length) of the version, by the host function (no GPU, no CRC check) */
+static int cmd_read(int argc, char **argv)
+{
+	if (argc < 7) usage();
+	char *e1 = NULL, *e2 = NULL;
+	errno = 0;
+	unsigned long long off = strtoull(argv[4], &e1, 10), len = strtoull(argv[5], &e2, 10);
+	/* digits only: strtoull alone would take a sign or leading blanks */
+	if (errno || argv[4][0] < '0' || argv[4][0] > '9' || *e1 || argv[5][0] < '0' || argv[5][0] > '9' || *e2) {
+		fprintf(stderr, "delta_read: offset and length are decimal byte counts\n");
+		return 1;
+	}
+	size_t rl, dl;
+	uint8_t *r = read_file(argv[2], &rl), *d = read_file(argv[3], &dl);
+	dg_buffer_t o = {0};
+	int rc = dg_read(r, rl, d, dl, off, len, &o);
+	free(r);
+	free(d);
+	if (rc) {
+		fprintf(stderr, "delta_read: %s\n", dg_status_string(rc));
+		return 1;
+	}
+	write_file(argv[6], o.data, o.len);
+	dg_buffer_free(&o);
+	return 0;
+}
+
 /* delta pick [--seed-len P] [--bins K] <version> <candidate>...: which candidate
  * to encode the version against, by the host functions (no GPU) */
 static int cmd_pick(int argc, char **argv)
@@ -542,6 +572,7 @@ int main(int argc, char **argv)
 	if (strcmp(argv[1], "compose") == 0) return cmd_compose(argc, argv);
 	if (strcmp(argv[1], "invert") == 0) return cmd_invert(argc, argv);
 	if (strcmp(argv[1], "pick") == 0) return cmd_pick(argc, argv);
+	if (strcmp(argv[1], "read") == 0) return cmd_read(argc, argv);
 	usage();
 	return 1;
 }

@@ -1,7 +1,7 @@
 // dg_hostutil.h — what the host files that touch the device share (dg_host.cpp,
 // dg_host_io.cpp and the transform plans' dg_inplace_host.cpp,
-// dg_update_host.cpp, dg_compose_host.cpp, dg_invert_host.cpp, and the sketch
-// plan's dg_sketch_host.cpp): device buffers, the stage-timing
+// dg_update_host.cpp, dg_compose_host.cpp, dg_invert_host.cpp, the sketch
+// plan's dg_sketch_host.cpp and the read plan's dg_read_host.cpp): device buffers, the stage-timing
 // event ring, the loader of the code objects that are loaded at run time, and
 // the small pieces of the plans and of the host-memory batch wrappers.
 // Internal; needs HIP.

@@ -916,6 +916,123 @@ int dg_invert_batch(dg_context_t *ctx, const uint8_t *const *r, const size_t *r_
                     const uint8_t *const *delta, const size_t *delta_len, uint32_t n,
                     dg_buffer_t *outs, int32_t *status);
 
+/* ── range reads: bytes [off, off + len) of a version kept as R and a delta ────
+ *
+ * What a version store does most: serve a read of part of a version without
+ * rebuilding the version.  The reference has no such function; the contract
+ * is its replay, sliced.  The result equals bytes [off, off + n) of what
+ * delta_apply_placed (apply.c:229-249) produces: a zeroed buffer of
+ * version_size bytes, then the commands in stream order, later writes over
+ * earlier ones (so an uncovered gap reads as zeros).  pread semantics, in 64
+ * bits: n = off >= version_size ? 0 : min(len, version_size - off).
+ *
+ * Standard deltas only.  Status, the first that applies:
+ *   DG_ERR_TOO_LARGE    r_len or delta_len of 4 GiB or more (for a plan: at
+ *                       create);
+ *   DG_ERR_MALFORMED    shorter than the 25-byte header, or another magic;
+ *   DG_ERR_UNSUPPORTED  the in-place flag is set: that replay reads the buffer
+ *                       it rewrites, so a slice of it needs the whole replay;
+ *   DG_ERR_MALFORMED    exactly what dg_decode_plan_run calls malformed:
+ *                       framing, an unknown command, a payload past the end,
+ *                       dst + len > version_size, a COPY's src + len > r_len
+ *                       (anywhere in the stream, not only in the range).  A
+ *                       missing END is accepted, as in decode.
+ *
+ * No CRC is checked.  dst_crc cannot be checked from a slice, and checking
+ * src_crc would read all of R for every request.  A store checks R once when
+ * it takes it in: dg_crc64_xz_batch_device over the references against
+ * dg_delta_info's src_crc.
+ *
+ * dg_read is pure host code: no context, no GPU.  One walk over the stream,
+ * which applies only the commands' intersections with the range; *out takes
+ * n bytes (free with dg_buffer_free; data is non-NULL on DG_OK even for n = 0). */
+int dg_read(const uint8_t *r, size_t r_len, const uint8_t *delta, size_t delta_len,
+            uint64_t off, uint64_t len, dg_buffer_t *out);
+
+/* ── range reads of a batch on the device ──────────────────────────────────
+ *
+ * Streams are fixed at create: stream i's reference is ref_len bytes at
+ * ref_off of the reference arena, its delta delta_len bytes at delta_off of
+ * the delta arena.  Requests are a device array given at run, any number of
+ * them per stream.  R and the deltas are only read.
+ *
+ * Index.  dg_read_plan_index is one launch, one block per stream: it parses
+ * and validates every stream once and leaves, in memory the plan owns, what
+ * lets a read start near its range: per stream a 32-byte head (status,
+ * version_size, whether the commands tile V in stream order) and 8 bytes per
+ * 1024 bytes of stream, at most delta_len / 128 + 64 bytes per stream
+ * (allocated at create; DG_ERR_NOMEM if that fails).  The layout is private.
+ * d_delta_offsets (n + 1 entries) and d_delta_status mean what they mean for
+ * dg_update_plan_run: with offsets, stream i is d_delta[d_delta_offsets[i] ..
+ * d_delta_offsets[i+1]) and delta_len only bounds it (a longer stream is
+ * DG_ERR_CAPACITY); a nonzero d_delta_status[i] is passed on and comes before
+ * every status above.  So dg_encode_plan_run -> dg_read_plan_index ->
+ * dg_read_plan_run chain on one stream with no host step.  Each stream's
+ * status goes to d_stream_status[i] (may be NULL) and is kept by the plan; for
+ * a standard stream it equals dg_decode_batch_device(ignore_hash = 1)'s.  The
+ * index describes the delta bytes as they were: run it again whenever they
+ * change.  A run before any index is DG_ERR_INVALID_ARG (dg_last_error says
+ * so); a plan of no streams needs none.
+ *
+ * Run.  One launch, one block per request, n_req <= max_requests
+ * (DG_ERR_INVALID_ARG otherwise); no allocation, no host synchronisation.
+ * Request j's status goes to d_status[j]: DG_ERR_INVALID_ARG for stream >=
+ * n_streams or reserved != 0, else its stream's status, else DG_OK with
+ * d_out_len[j] = n and the slice in d_out[out_off .. out_off + n).  Bytes
+ * [n, len) of the slot are not touched; on a failing status n = 0 and the
+ * slot is not touched; nothing outside the slots is written for any status.
+ * Slots that overlap are the caller's error (unspecified inside the overlap).
+ * out_off may have any alignment; d_out must be 16-byte aligned.
+ *
+ * Cost.  A stream whose commands tile V in stream order (what every encoder,
+ * dg_compose and dg_invert emit) is entered at the index entry before the
+ * range and left after it: the work is proportional to the range.  Any other
+ * valid stream (commands out of order, overlapping writes, gaps) is correct
+ * but costs a parse of the whole stream per request.
+ *
+ * Containment.  Whatever the arenas hold, a stale index after the deltas
+ * were overwritten included, a run reads only the streams' reference and
+ * delta bytes (the delta in whole aligned 16-byte words that hold one of its
+ * bytes, as decode does) and writes only inside the requests' slots: the read
+ * kernel checks every COPY's src + len against ref_len and clips every store
+ * itself.  Results under a stale index are otherwise unspecified.
+ *
+ * The kernels live in dg_read.hsaco beside libdeltagpu.so and are loaded on
+ * first use; DG_ERR_HIP with the path in dg_last_error when it is missing.
+ * Stage timing as for the update plan, of runs: "read" (the kernel), "total". */
+typedef struct {
+	uint64_t ref_off, ref_len;
+	uint64_t delta_off, delta_len;  /* with d_delta_offsets: delta_len only bounds the stream */
+} dg_read_stream_t;
+typedef struct {
+	uint32_t stream, off, len;
+	uint32_t reserved;              /* 0 */
+	uint64_t out_off;               /* the slot: d_out[out_off .. out_off + len) */
+} dg_read_req_t;
+typedef struct dg_read_plan dg_read_plan_t;
+
+int dg_read_plan_create(dg_context_t *ctx, const dg_read_stream_t *streams /* host */, uint32_t n_streams,
+                        uint32_t max_requests, dg_read_plan_t **out);
+int dg_read_plan_index(dg_read_plan_t *plan, const uint8_t *d_delta,
+                       const uint64_t *d_delta_offsets, const int32_t *d_delta_status,
+                       int32_t *d_stream_status, void *stream);
+int dg_read_plan_run(dg_read_plan_t *plan, const uint8_t *d_ref, const uint8_t *d_delta,
+                     const dg_read_req_t *d_reqs, uint32_t n_req, uint8_t *d_out,
+                     uint32_t *d_out_len, int32_t *d_status, void *stream);
+int dg_read_plan_set_timing(dg_read_plan_t *plan, int slots);
+int dg_read_plan_stage_times(dg_read_plan_t *plan, float *ms, const char **names, int n);
+void dg_read_plan_destroy(dg_read_plan_t *plan);
+
+/* Host buffers: request j (reqs[j].stream, .off, .len; out_off is ignored)
+ * reads from refs[stream] and deltas[stream]; outs[j] takes the n bytes
+ * (malloc'd; free with dg_buffer_free; left empty on a failing status).
+ * Returns DG_OK (per-request failures in status) or the first failure when
+ * status is NULL. */
+int dg_read_batch(dg_context_t *ctx, const uint8_t *const *refs, const size_t *ref_len,
+                  const uint8_t *const *deltas, const size_t *delta_len, uint32_t n_streams,
+                  const dg_read_req_t *reqs /* host */, uint32_t n_req,
+                  dg_buffer_t *outs, int32_t *status);
+
 /* ── reference selection: resemblance sketches and base matching ─────────────
  *
  * Every entry point above starts from a pair: the caller knows which R a V is
