@@ -19,6 +19,11 @@ Names and argument meanings follow the reference's interface for this path:
 * ``invert(R, A)`` / ``InvertPlan`` / ``invert_batch`` — R and delta(R -> V)
   turned into delta(V -> R) without V (no reference counterpart; the normal
   form is stated in ``include/delta_gpu.h``).
+* ``segment_pairs`` / ``SplicePlan`` / ``splice`` / ``splice_batch`` /
+  ``encode_large`` — one large pair cut into segments of V against windows of
+  R, encoded as an ordinary batch, the segment deltas spliced into one
+  standard delta (no reference counterpart; rule, contract and normal form are
+  stated in ``include/delta_gpu.h``).
 * ``read_range(R, delta, off, length)`` / ``ReadPlan`` / ``read_ranges`` — bytes
   [off, off + length) of the version a standard delta makes of R, without
   rebuilding the version (no reference counterpart: the replay of
@@ -62,6 +67,7 @@ from ._lib import (  # noqa: F401
     ComposePlan,
     InvertDesc,
     InvertPlan,
+    SplicePlan,
     ReadPlan,
     ReadReq,
     ReadStream,
@@ -100,6 +106,11 @@ from ._lib import (  # noqa: F401
     compose_batch,
     invert,
     invert_batch,
+    segment_pairs,
+    splice,
+    splice_batch,
+    sketch_windows,
+    encode_large,
     read_range,
     read_ranges,
     sketch,
@@ -118,6 +129,7 @@ __all__ = [
     "MAX_TABLE_SIZE", "BUF_CAP", "Context", "DeltaError", "DiffOptions", "EncodePlan", "DecodePlan", "InplacePlan", "UpdatePlan",
     "ComposeDesc", "ComposePlan", "compose", "compose_batch",
     "InvertDesc", "InvertPlan", "invert", "invert_batch",
+    "SplicePlan", "segment_pairs", "splice", "splice_batch", "sketch_windows", "encode_large",
     "ReadPlan", "ReadReq", "ReadStream", "read_range", "read_ranges",
     "SketchPlan", "sketch", "sketch_batch", "match_sketches", "match_sketches_device", "pick_bases", "SKETCH_BINS", "SKETCH_EMPTY",
     "MATCH_NONE", "MATCH_ALL", "MATCH_NOT_SELF", "MATCH_EARLIER",

@@ -243,6 +243,21 @@ def _load() -> C.CDLL:
         "dg_invert_plan_destroy": (None, [vp]),
         "dg_invert_batch": (C.c_int, [vp, C.POINTER(u8p), C.POINTER(sz), C.POINTER(u8p), C.POINTER(sz), u32,
                                       C.POINTER(Buffer), C.POINTER(i32)]),
+        "dg_segment_pairs": (C.c_int, [C.POINTER(Pair), u32, u64, u64, C.POINTER(Pair), u64, C.POINTER(u32)]),
+        "dg_splice": (C.c_int, [C.POINTER(Pair), C.POINTER(Pair), u32, C.POINTER(u8p), C.POINTER(sz), C.POINTER(i32),
+                                C.c_uint8 * 8, C.POINTER(Buffer)]),
+        "dg_splice_plan_create": (C.c_int, [vp, C.POINTER(Pair), u32, C.POINTER(Pair), C.POINTER(u32), u32,
+                                            C.POINTER(u64), C.POINTER(vp)]),
+        "dg_splice_plan_create_for": (C.c_int, [vp, vp, C.POINTER(Pair), C.POINTER(u32), u32, C.POINTER(vp)]),
+        "dg_splice_plan_output_bound": (u64, [vp]),
+        "dg_splice_plan_run": (C.c_int, [vp, vp, vp, vp, vp, vp, u64, vp, vp, vp]),
+        "dg_splice_plan_set_timing": (C.c_int, [vp, C.c_int]),
+        "dg_splice_plan_stage_times": (C.c_int, [vp, C.POINTER(C.c_float), C.POINTER(C.c_char_p), C.c_int]),
+        "dg_splice_plan_destroy": (None, [vp]),
+        "dg_splice_batch": (C.c_int, [vp, C.POINTER(Pair), u32, C.POINTER(Pair), C.POINTER(u32), C.POINTER(u8p),
+                                      C.POINTER(sz), C.POINTER(i32), u8p, C.POINTER(Buffer), C.POINTER(i32)]),
+        "dg_encode_large": (C.c_int, [vp, C.c_int, u8p, sz, u8p, sz, C.POINTER(DiffOptions), u64, u64,
+                                      C.POINTER(Buffer)]),
         "dg_read": (C.c_int, [u8p, sz, u8p, sz, u64, u64, C.POINTER(Buffer)]),
         "dg_read_plan_create": (C.c_int, [vp, C.POINTER(ReadStream), u32, u32, C.POINTER(vp)]),
         "dg_read_plan_index": (C.c_int, [vp, vp, vp, vp, vp, vp]),
@@ -850,6 +865,195 @@ def invert_batch(items: Sequence[Tuple[bytes, bytes]], ctx: Optional[Context] = 
         if st[i]:
             raise DeltaError(st[i], f"delta {i}")
     return res
+
+
+# ── one large pair: segments, windows and the splice of the segments' deltas ──
+
+def _pairs(items):
+    n = len(items)
+    return (Pair * max(n, 1))(*[Pair(*map(int, p)) for p in items])
+
+
+def segment_pairs(wholes, seg_bytes: int = 1 << 20, window_bytes: int = 1 << 20):
+    """The fixed segmentation rule (dg_segment_pairs, host only).  wholes: one
+    (r_off, r_len, v_off, v_len) or a sequence of them; returns (segments,
+    seg_first): the segments of every group as (r_off, r_len, v_off, v_len),
+    group after group, and each group's first segment (n_groups + 1 entries)."""
+    if wholes and isinstance(wholes[0], int):
+        wholes = [wholes]
+    n = len(wholes)
+    wa = _pairs(wholes)
+    first = (C.c_uint32 * (n + 1))()
+    rc = lib.dg_segment_pairs(wa, n, seg_bytes, window_bytes, None, 0, first)
+    if rc:
+        raise DeltaError(rc, "dg_segment_pairs")
+    total = first[n]
+    segs = (Pair * max(total, 1))()
+    rc = lib.dg_segment_pairs(wa, n, seg_bytes, window_bytes, segs, total, first)
+    if rc:
+        raise DeltaError(rc, "dg_segment_pairs")
+    return [(s.r_off, s.r_len, s.v_off, s.v_len) for s in segs[:total]], list(first)
+
+
+def splice(segments, deltas: Sequence[bytes], whole, src_crc: bytes, seg_status=None) -> bytes:
+    """The deltas of one group's segments -> one standard delta of the whole
+    pair, in normal form (dg_splice): host only, and none of R or V is needed.
+    src_crc: the 8 header bytes of CRC-64/XZ(R)."""
+    n = len(segments)
+    keep = [bytes(d) for d in deltas]
+    if len(keep) != n or len(src_crc) != 8:
+        raise ValueError("one delta per segment and an 8-byte src_crc")
+    dp = (C.POINTER(C.c_uint8) * max(n, 1))(*[_u8(d) for d in keep])
+    dl = (C.c_size_t * max(n, 1))(*[len(d) for d in keep])
+    st = (C.c_int32 * max(n, 1))(*seg_status) if seg_status is not None else None
+    out = Buffer()
+    rc = lib.dg_splice(_pairs([whole]), _pairs(segments), n, dp, dl, st, (C.c_uint8 * 8)(*src_crc), C.byref(out))
+    if rc:
+        raise DeltaError(rc, "dg_splice")
+    res = C.string_at(out.data, out.len) if out.len else b""
+    lib.dg_buffer_free(C.byref(out))
+    return res
+
+
+class SplicePlan(_Plan):
+    """dg_splice_plan_t: the segment deltas of a batch of large pairs spliced on
+    the device into one standard delta per pair.  segments, wholes: (r_off,
+    r_len, v_off, v_len); seg_first: n_groups + 1 entries; caps: the most bytes
+    each segment's delta may have (None: no bound), or for_plan: the EncodePlan
+    that encodes the segments (pass its offsets and status to run)."""
+
+    _prefix = "dg_splice_plan"
+
+    def __init__(self, ctx: Context, wholes, seg_first, segments=None, caps=None,
+                 for_plan: Optional["EncodePlan"] = None):
+        self.ctx = ctx
+        h = C.c_void_p()
+        ng = len(wholes)
+        fa = (C.c_uint32 * (ng + 1))(*seg_first)
+        if for_plan is not None:
+            ctx.check(lib.dg_splice_plan_create_for(ctx.handle, for_plan.handle, _pairs(wholes), fa, ng, C.byref(h)),
+                      "dg_splice_plan_create_for")
+            self.n_seg = for_plan.n
+        else:
+            ns = len(segments)
+            ca = (C.c_uint64 * max(ns, 1))(*caps) if caps is not None else None
+            ctx.check(lib.dg_splice_plan_create(ctx.handle, _pairs(segments), ns, _pairs(wholes), fa, ng, ca, C.byref(h)),
+                      "dg_splice_plan_create")
+            self.n_seg = ns
+        self._own(h)
+        self.n = ng
+
+    @property
+    def output_bound(self) -> int:
+        return lib.dg_splice_plan_output_bound(self.handle)
+
+    def run(self, d_deltas: int, d_offsets: int, d_src_crc: int, d_out: int, out_cap: int, d_out_offsets: int,
+            d_status: int, d_seg_status: int = 0, stream: int = 0):
+        self.ctx.check(lib.dg_splice_plan_run(self.handle, d_deltas or None, d_offsets or None, d_seg_status or None,
+                                              d_src_crc or None, d_out or None, out_cap, d_out_offsets, d_status,
+                                              stream or None), "dg_splice_plan_run")
+
+
+def splice_batch(groups, ctx: Optional[Context] = None, status: bool = False):
+    """Groups of (segments, deltas, whole, src_crc[, seg_status]) spliced on the
+    device in one batch (dg_splice_batch); equal to splice group by group.
+    Raises DeltaError for the first failing group; with status=True returns
+    (results, statuses) instead, a failed group's result being b""."""
+    ctx = ctx or default_context()
+    ng = len(groups)
+    if ng == 0:
+        return ([], []) if status else []
+    segs, keep, first, sst, any_st = [], [], [0], [], False
+    for grp in groups:
+        segs += list(grp[0])
+        keep += [bytes(d) for d in grp[1]]
+        if len(grp) > 4 and grp[4] is not None:
+            sst += list(grp[4])
+            any_st = True
+        else:
+            sst += [0] * len(grp[0])
+        first.append(len(segs))
+    if len(keep) != len(segs):
+        raise ValueError("one delta per segment")
+    ns = len(segs)
+    dp = (C.POINTER(C.c_uint8) * max(ns, 1))(*[_u8(d) for d in keep])
+    dl = (C.c_size_t * max(ns, 1))(*[len(d) for d in keep])
+    crc = b"".join(bytes(grp[3]) for grp in groups)
+    outs = (Buffer * ng)()
+    st = (C.c_int32 * ng)()
+    ctx.check(lib.dg_splice_batch(ctx.handle, _pairs([grp[2] for grp in groups]), ng, _pairs(segs),
+                                  (C.c_uint32 * (ng + 1))(*first), dp, dl,
+                                  (C.c_int32 * max(ns, 1))(*sst) if any_st else None, _u8(crc), outs, st),
+              "dg_splice_batch")
+    res = []
+    for i in range(ng):
+        res.append(C.string_at(outs[i].data, outs[i].len) if outs[i].len else b"")
+        lib.dg_buffer_free(C.byref(outs[i]))
+    if status:
+        return res, list(st)
+    for i in range(ng):
+        if st[i]:
+            raise DeltaError(st[i], f"group {i}")
+    return res
+
+
+def sketch_windows(R: bytes, V: bytes, seg_bytes: int = 1 << 20, window_bytes: int = 1 << 20, host: bool = False,
+                   p: int = SEED_LEN, k: int = SKETCH_BINS, ctx: Optional[Context] = None):
+    """The segments of (R, V) with each window chosen by resemblance instead of
+    by position, for drift: an insertion longer than the window starves every
+    later fixed window.  Candidate windows R[max(0, cS - W), min(|R|, cS + S + W))
+    for c = 0 .. ceil(|R| / S) - 1 are sketched, V's segments are the targets,
+    matched with mode "all"; a target without a match keeps the fixed rule's
+    window.  host=True sketches and matches with the host functions.  Returns
+    the segments as segment_pairs does."""
+    S, W = seg_bytes, window_bytes
+    segs, _ = segment_pairs((0, len(R), 0, len(V)), S, W)
+    cands = [(max(0, c * S - W), min(len(R), c * S + S + W)) for c in range((len(R) + S - 1) // S)]
+    if not cands:
+        return segs
+    bufs = [R[a:b] for a, b in cands] + [V[vo:vo + vl] for _, _, vo, vl in segs]
+    if host:
+        sk = [sketch(b, p, k) for b in bufs]
+        best = match_sketches(sk[len(cands):], sk[:len(cands)], k, "all")
+    else:
+        ctx = ctx or default_context()
+        sk = sketch_batch(bufs, p, k, ctx)
+        best = match_sketches(sk[len(cands):], sk[:len(cands)], k, "all")
+    out = []
+    for seg, (b, _, _) in zip(segs, best):
+        if b == MATCH_NONE:
+            out.append(seg)
+        else:
+            out.append((cands[b][0], cands[b][1] - cands[b][0], seg[2], seg[3]))
+    return out
+
+
+def encode_large(R: bytes, V: bytes, algorithm="onepass", seg_bytes: int = 1 << 20, window_bytes: int = 1 << 20,
+                 windows: str = "fixed", p: int = SEED_LEN, q: int = TABLE_SIZE, buf_cap: int = BUF_CAP,
+                 max_table: int = MAX_TABLE_SIZE, splay: bool = False, inplace: bool = False,
+                 policy: str = "localmin", ctx: Optional[Context] = None) -> bytes:
+    """One large pair encoded as segments of V against windows of R, the
+    segment deltas spliced on the device into one standard delta (every wave
+    of the device at work instead of one).  windows="fixed": the rule of
+    segment_pairs, all on the device (dg_encode_large); "sketch" /
+    "sketch_host": windows chosen by sketch_windows, the segments encoded as
+    one batch and spliced on the device."""
+    ctx = ctx or default_context()
+    if windows == "fixed":
+        out = Buffer()
+        o = _opts(p, q, buf_cap, max_table, splay=splay, inplace=inplace, policy=policy)
+        ctx.check(lib.dg_encode_large(ctx.handle, _algo(algorithm), _u8(R), len(R), _u8(V), len(V), C.byref(o),
+                                      seg_bytes, window_bytes, C.byref(out)), "dg_encode_large")
+        res = C.string_at(out.data, out.len)
+        lib.dg_buffer_free(C.byref(out))
+        return res
+    if windows not in ("sketch", "sketch_host"):
+        raise ValueError(f"Unknown window rule: {windows}")
+    segs = sketch_windows(R, V, seg_bytes, window_bytes, host=windows == "sketch_host", p=p, ctx=ctx)
+    deltas = encode_batch([(R[ro:ro + rl], V[vo:vo + vl]) for ro, rl, vo, vl in segs], algorithm, p, q, buf_cap,
+                          max_table, ctx, splay)
+    d = splice_batch([(segs, deltas, (0, len(R), 0, len(V)), crc64_xz(R, ctx))], ctx)[0]
+    return make_inplace(R, d, policy) if inplace else d
 
 
 class ReadPlan(_Plan):

@@ -114,7 +114,11 @@ static void usage(void)
 	    "  --inplace        Produce in-place delta\n"
 	    "  --policy P       Cycle policy: localmin (default), constant\n"
 	    "  --verbose        Print diagnostics\n"
-	    "  --splay          Use splay tree instead of hash table (greedy only)\n",
+	    "  --splay          Use splay tree instead of hash table (greedy only)\n"
+	    "  --segment-size N   encode: cut the version into segments of N bytes (a multiple of 16,\n"
+	    "                     k/M/B suffix ok), encode them as one batch and splice the deltas\n"
+	    "  --segment-window W bytes of the reference before and after a segment's own range\n"
+	    "                     that it may copy from (default N)\n",
 	    DG_SEED_LEN, (unsigned long)DG_TABLE_SIZE, (unsigned long)DG_MAX_TABLE_SIZE);
 	exit(1);
 }
@@ -153,7 +157,11 @@ static int cmd_encode(int argc, char **argv)
 		{"policy", required_argument, NULL, 'p'},
 		{"verbose", no_argument, NULL, 'v'},
 		{"splay", no_argument, NULL, 'y'},
+		{"segment-size", required_argument, NULL, 'S'},
+		{"segment-window", required_argument, NULL, 'W'},
 		{NULL, 0, NULL, 0}};
+	uint64_t seg_bytes = 0, seg_window = 0;
+	int have_window = 0;
 	optind = 6;
 	int opt;
 	while ((opt = getopt_long(argc, argv, "", lo, NULL)) != -1) {
@@ -163,6 +171,8 @@ static int cmd_encode(int argc, char **argv)
 		case 'x': o.max_table = parse_size_suffix(optarg); break;
 		case 'v': o.flags |= 1ull << DG_OPT_VERBOSE; break;
 		case 'i': o.flags |= 1ull << DG_OPT_INPLACE; break;
+		case 'S': seg_bytes = parse_size_suffix(optarg); break;
+		case 'W': seg_window = parse_size_suffix(optarg); have_window = 1; break;
 		case 'y':
 			if (algo != DG_ALGO_GREEDY) {
 				fprintf(stderr, "--splay is not provided by the MI355X build\n");
@@ -181,12 +191,20 @@ static int cmd_encode(int argc, char **argv)
 		fprintf(stderr, "error: --seed-len must be >= 1\n");
 		return 1;
 	}
+	if (have_window && !seg_bytes) {
+		fprintf(stderr, "error: --segment-window needs --segment-size\n");
+		return 1;
+	}
+	if (!have_window) seg_window = seg_bytes;
 	size_t rl, vl;
 	uint8_t *r = read_file(ref_path, &rl), *v = read_file(ver_path, &vl);
 	dg_context_t *ctx = ctx_or_die();
 	dg_buffer_t d = {0};
 	double t0 = now();
-	int rc = dg_encode(ctx, algo, r, rl, v, vl, &o, &d);
+	/* --segment-size: the pair as segments of V against windows of R, their
+	 * deltas spliced on the device into one standard delta */
+	int rc = seg_bytes ? dg_encode_large(ctx, algo, r, rl, v, vl, &o, seg_bytes, seg_window, &d)
+	                   : dg_encode(ctx, algo, r, rl, v, vl, &o, &d);
 	double t1 = now();
 	if (rc) {
 		fprintf(stderr, "delta: encode failed: %s (%s)\n", dg_status_string(rc), dg_last_error(ctx));

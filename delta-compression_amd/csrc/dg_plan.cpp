@@ -678,6 +678,56 @@ int invert_plan_geometry_for(const EncodePlanView& e, uint32_t n, InvertGeometry
 	return invert_finish(g, err);
 }
 
+// ── splice plan: groups, segments, CRC weights ──
+
+int splice_plan_geometry(const dg_pair_t* segs, uint32_t n_seg, const dg_pair_t* wholes, const uint32_t* seg_first,
+                         uint32_t n_groups, const uint64_t* caps, SpliceGeometry& g, std::string& err) {
+	g.descs.assign(n_seg, dgsp::SpDesc{});
+	g.groups.assign(n_groups, dgsp::SpGroup{});
+	g.bound = 0;
+	if (seg_first[0] != 0 || seg_first[n_groups] != n_seg)
+		return fail(err, DG_ERR_INVALID_ARG, "splice plan: seg_first does not run from 0 to the segment count");
+	constexpr uint64_t kLimit = (1ull << 32) - (1ull << 20);
+	for (uint32_t k = 0; k < n_groups; ++k) {
+		const dg_pair_t& w = wholes[k];
+		const uint32_t first = seg_first[k], end = seg_first[k + 1];
+		if (end <= first || end > n_seg) return fail(err, DG_ERR_INVALID_ARG, "splice plan: group %u has no segment", k);
+		if (w.r_len >= kLimit || w.v_len >= kLimit)
+			return fail(err, DG_ERR_TOO_LARGE, "splice plan: group %u: buffers of 4 GiB or more do not fit the u32 format", k);
+		g.groups[k] = dgsp::SpGroup{first, end - first, (uint32_t)w.v_len, 0};
+		uint64_t at = w.v_off;
+		for (uint32_t j = first; j < end; ++j) {
+			const dg_pair_t& s = segs[j];
+			if (s.v_off != at || s.v_len > w.v_off + w.v_len - at)
+				return fail(err, DG_ERR_INVALID_ARG, "splice plan: segment %u does not continue the tiling of its group's V", j);
+			at += s.v_len;
+			if (s.r_off < w.r_off || s.r_off - w.r_off > w.r_len || s.r_len > w.r_len - (s.r_off - w.r_off))
+				return fail(err, DG_ERR_INVALID_ARG, "splice plan: segment %u: its window is not inside its group's R", j);
+			const uint64_t cap = caps ? caps[j] : (1ull << 32) - 1;
+			if (cap >= (1ull << 32))
+				return fail(err, DG_ERR_TOO_LARGE, "splice plan: a stream of 4 GiB or more does not fit the u32 format");
+			dgsp::SpDesc& d = g.descs[j];
+			d.cap = cap;
+			d.rebase = (uint32_t)(s.r_off - w.r_off);
+			d.r_len = (uint32_t)s.r_len;
+			d.v_rel = (uint32_t)(s.v_off - w.v_off);
+			d.v_len = (uint32_t)s.v_len;
+			d.group = k;
+			if (caps) g.bound += cap;
+		}
+		if (at != w.v_off + w.v_len)
+			return fail(err, DG_ERR_INVALID_ARG, "splice plan: group %u: the segments do not cover its V", k);
+		// x^(8 * suffix), from the last segment back: one power per segment
+		uint64_t shift = 1ULL << 63;
+		for (uint32_t j = end; j-- > first;) {
+			g.descs[j].shift = shift;
+			if (segs[j].v_len) shift = gf2_mul(shift, gf2_xpow(8 * segs[j].v_len));
+		}
+		if (caps) g.bound += 1;
+	}
+	return DG_OK;
+}
+
 // ── sketch plan: the (span, chunk) work list ──
 
 int sketch_plan_geometry(const dg_span_t* spans, uint32_t n, uint32_t p, uint32_t K, uint32_t chunk_bytes,

@@ -14,6 +14,7 @@
 #include "dg_invert_dev.h"
 #include "dg_layout.h"
 #include "dg_sketch_dev.h"
+#include "dg_splice_dev.h"
 
 namespace dg {
 
@@ -138,6 +139,22 @@ struct InvertGeometry {
 uint32_t invert_max_copies(uint64_t cap);
 int invert_plan_geometry(const dg_invert_desc_t* descs, uint32_t n, InvertGeometry& g, std::string& err);
 int invert_plan_geometry_for(const EncodePlanView& e, uint32_t n, InvertGeometry& g, std::string& err);
+
+// ── the splice plan (dg_splice_host.cpp) and the host splice (dg_splice.cpp) ──
+struct SpliceGeometry {
+	std::vector<dgsp::SpDesc> descs;     // per segment
+	std::vector<dgsp::SpGroup> groups;
+	uint64_t bound = 0;   // dg_splice_plan_output_bound: the capacities' sum + one byte per group; 0 without capacities
+};
+// Checks the groups (seg_first: n_groups + 1 ascending entries from 0 to n_seg,
+// every group with a segment), that each group's segments tile its V span in
+// order and that every window lies inside its R span (DG_ERR_INVALID_ARG); an
+// r_len or v_len at or above 4 GiB - 1 MiB, the encode plan's limit, or a
+// capacity of 4 GiB or more is DG_ERR_TOO_LARGE.  caps may be NULL: no bound.
+// Fills the descriptors: rebase, window, place in V and the weight of the
+// segment's dst_crc in the group's, x^(8 * bytes of V after it).
+int splice_plan_geometry(const dg_pair_t* segs, uint32_t n_seg, const dg_pair_t* wholes, const uint32_t* seg_first,
+                         uint32_t n_groups, const uint64_t* caps, SpliceGeometry& g, std::string& err);
 
 // ── the sketch plan (dg_sketch_host.cpp) ──
 struct SketchGeometry {

@@ -916,6 +916,184 @@ int dg_invert_batch(dg_context_t *ctx, const uint8_t *const *r, const size_t *r_
                     const uint8_t *const *delta, const size_t *delta_len, uint32_t n,
                     dg_buffer_t *outs, int32_t *status);
 
+/* ── one large pair: segments of V, windows of R, and the splice of their deltas ──
+ *
+ * The encoders give one wavefront to a pair, so one large pair would run on one
+ * wave.  A large pair is instead cut into segments of V, each encoded against a
+ * window of R as one dg_pair_t of an ordinary encode plan (thousands of waves),
+ * and the k segment deltas are spliced into ONE standard DLT\x03 delta R -> V.
+ * The splice is a pure transform of command streams, in the family of
+ * composition and inversion: it needs none of R or V.  The result is a
+ * different, documented encoder's output (a segment sees matches only inside
+ * its window), a standard delta that every decoder accepts.  (The reference has
+ * no such step.)
+ *
+ * Segmentation rule (dg_segment_pairs).  For a whole pair (r_off, r_len, v_off,
+ * v_len), seg_bytes S > 0 and window_bytes W, both multiples of 16, the count
+ * is k = max(1, ceil(v_len / S)); segment j is V[jS, min((j + 1) S, v_len)); its
+ * window is R[a, max(a, b)) with lo = min(jS, r_len), a = lo - min(lo, W), b =
+ * min(r_len, jS + S + W).  Pure arithmetic: with whole offsets that are multiples
+ * of 16 every segment offset is one too, so the encode plan takes its LDS-window
+ * kernels.  For n_groups whole pairs the segments are written group after group
+ * and seg_first[g] (n_groups + 1 entries) is group g's first segment.  With segs
+ * == NULL only seg_first is filled (the count).  DG_ERR_INVALID_ARG for S == 0
+ * or an S or W that is no multiple of 16; DG_ERR_TOO_LARGE for an r_len or v_len
+ * at or above 4 GiB - 1 MiB (the encode plan's limit) or more than 2^32 - 1
+ * segments; DG_ERR_CAPACITY when segs_cap entries do not hold them.  Host only.
+ *
+ * Inputs of the splice, per group.  A group is one large pair: a span `whole` of
+ * the two arenas and n_seg >= 1 consecutive segments seg[j], the very array given
+ * to dg_encode_plan_create.  The segments' V spans tile [v_off, v_off + v_len)
+ * exactly and in order; empty segments are allowed.  Every R window lies inside
+ * [r_off, r_off + r_len); windows may overlap, repeat, leave gaps and be empty.
+ * A_j is a standard, sequentially placed delta of seg[j] (as for dg_compose);
+ * its version_size equals seg[j].v_len.
+ *
+ * Provenance.  Walk the segments in order and each A_j's commands in order.  An
+ * ADD contributes its literal bytes; a COPY(src, len) contributes COPY(src +
+ * seg[j].r_off - whole.r_off, len); zero-length commands contribute nothing.
+ *
+ * Normal form.  Composition's rule: consecutive literal pieces become one ADD;
+ * consecutive COPY pieces become one COPY whenever the second starts in R where
+ * the first ends; inside a segment's stream and across segment seams alike,
+ * through any number of empty segments.  dst is sequential, no zero-length
+ * command is emitted, one END byte closes the stream, the flag byte is 0 and
+ * version_size = whole.v_len.  The result is a function of the byte-provenance
+ * map of V alone: R == V cut into any number of segments whose windows contain
+ * them splices to one COPY (25 + 13 + 1 = 39 bytes); a V unrelated to R to one
+ * ADD of |V|; one segment whose window is all of R to compose(A, identity(V)),
+ * A's own normal form.  The host function, the device path and the tests'
+ * Python model produce it byte for byte.
+ *
+ * CRCs.  src_crc is the CRC-64/XZ of all of R: the windows need not cover R, so
+ * the caller supplies it (device: one u64 per group as dg_crc64_xz_batch_device
+ * writes it; host: 8 bytes, big-endian as in the header).  dst_crc is not
+ * recomputed from V: it is combined from the segments' own header dst_crc
+ * values, crc(X || Y) = crc(X) x^(8 |Y|) + crc(Y) in GF(2)[x] mod P.  The
+ * weights x^(8 * bytes after the segment) are computed once per segment at plan
+ * creation; the device multiplies once per segment and reduces with XOR.  The
+ * spliced header costs no pass over V.
+ *
+ * Status, per group; first match wins:
+ *   (incoming)          the first nonzero incoming segment status, in segment
+ *                       order, is passed on;
+ *   DG_ERR_MALFORMED    what the siblings call malformed, in any segment stream
+ *                       (magic, framing, an unknown command, a payload past the
+ *                       end); a COPY with src + len > seg[j].r_len: the splicer
+ *                       knows the window, and rebased such a COPY would read
+ *                       valid but wrong bytes of R;
+ *   DG_ERR_CAPACITY     (device) a stream longer than its capacity;
+ *   DG_ERR_UNSUPPORTED  an in-place flag; placement not sequential; lengths that
+ *                       do not sum to version_size; version_size != seg[j].v_len;
+ *   DG_ERR_TOO_LARGE    the spliced delta would be 4 GiB or more (host: also a
+ *                       stream of 4 GiB or more);
+ *   DG_ERR_CAPACITY     (device) the group's output ends past out_cap.
+ * A failed group's output is empty and its neighbours are untouched; for a
+ * group that fails on out_cap the offsets still count its size.
+ *
+ * Geometry errors (dg_splice, dg_splice_plan_create*): DG_ERR_INVALID_ARG for
+ * segments that do not tile V in order, a window outside R, a group without a
+ * segment or a seg_first that does not run from 0 to n_seg; DG_ERR_TOO_LARGE for
+ * an r_len or v_len at or above 4 GiB - 1 MiB or a capacity of 4 GiB or more.
+ *
+ * dg_splice is pure host code (no context, no GPU), linear in its input; *out
+ * is malloc'd.  seg_status may be NULL (every segment DG_OK). */
+int dg_segment_pairs(const dg_pair_t *wholes, uint32_t n_groups, uint64_t seg_bytes,
+                     uint64_t window_bytes, dg_pair_t *segs /* or NULL */, uint64_t segs_cap,
+                     uint32_t *seg_first /* n_groups + 1 */);
+int dg_splice(const dg_pair_t *whole, const dg_pair_t *segs, uint32_t n_seg,
+              const uint8_t *const *deltas, const size_t *delta_len,
+              const int32_t *seg_status /* or NULL */, const uint8_t src_crc[DG_CRC_SIZE],
+              dg_buffer_t *out);
+
+/* ── the splice of a batch of groups on the device ─────────────────────────
+ *
+ * The same transform, byte for byte.  Segment j's stream is
+ * d_deltas[d_offsets[j] .. d_offsets[j + 1]) (n_seg + 1 entries, as
+ * dg_encode_plan_run writes them; required) and its capacity only bounds its
+ * length; d_seg_status (may be NULL) as dg_encode_plan_run writes it.  The
+ * groups' deltas are packed like the encode plan's output, group g at
+ * d_out[d_out_offsets[g] .. d_out_offsets[g + 1]), n_groups + 1 offsets.
+ *
+ * A run is three kernels and the library's size scan on one stream: no
+ * allocation, no host synchronisation, graph-capturable like its siblings.
+ *   map      one wave per segment parses and validates its stream and leaves a
+ *            fixed-size summary: status, the bytes of its own normal form, its
+ *            first run's kind / start in R / length, its last run's kind / end
+ *            in R / length, whether it is one run, its weighted dst_crc;
+ *   resolve  one wave per group walks the summaries 64 at a time with wave
+ *            scans and a carry: every seam, every segment's place in the
+ *            output, whether its first run continues its predecessor's, the
+ *            whole length of a run that crosses seams; status, size, dst_crc;
+ *   scan     the groups' sizes into d_out_offsets;
+ *   emit     one wave per segment parses again and writes rebased commands and
+ *            payloads inside its own resolved range; the first segment's block
+ *            writes the header, the last one the END byte.
+ * So dg_encode_plan_run(segments) -> dg_splice_plan_run is a large-pair encoder
+ * on one stream with no host step, and -> dg_inplace_plan_run ->
+ * dg_update_plan_run, dg_compose_plan_run, dg_invert_plan_run and
+ * dg_read_plan_index follow as for any delta.
+ *
+ * Sizing.  d_out_offsets always receives the true sizes.  The splice of a group
+ * is never longer than its segment deltas together plus one byte:
+ * dg_splice_plan_output_bound is the sum of the capacities plus one byte per
+ * group (a plan made from an encode plan uses the encoder's bounds; 0 for a
+ * plan created without capacities).  A run with d_out = NULL and out_cap = 0 is
+ * the sizing run, as for dg_compose_plan_run.
+ *
+ * Work memory is 56 + 16 bytes per segment, allocated at plan creation
+ * (DG_ERR_NOMEM when it cannot be had); no per-command tables.  n_groups == 0
+ * with n_seg == 0 is a valid empty plan.  One wave parses and writes one
+ * segment's delta, so the emit stage's parallelism is the segment count.
+ *
+ * The kernels live in dg_splice.hsaco beside libdeltagpu.so and are loaded on
+ * first use; DG_ERR_HIP with the path in dg_last_error when it is missing.
+ * Stage timing as for the in-place plan: "map", "resolve", "scan", "emit",
+ * "total". */
+typedef struct dg_splice_plan dg_splice_plan_t;
+
+int dg_splice_plan_create(dg_context_t *ctx, const dg_pair_t *segs /* host */, uint32_t n_seg,
+                          const dg_pair_t *wholes, const uint32_t *seg_first /* n_groups + 1 */,
+                          uint32_t n_groups, const uint64_t *seg_caps /* n_seg, or NULL */,
+                          dg_splice_plan_t **out);
+/* Segments and capacities from the encode plan that encodes them; pass
+ * dg_encode_plan_run's offsets and statuses to the run. */
+int dg_splice_plan_create_for(dg_context_t *ctx, const dg_encode_plan_t *enc,
+                              const dg_pair_t *wholes, const uint32_t *seg_first,
+                              uint32_t n_groups, dg_splice_plan_t **out);
+uint64_t dg_splice_plan_output_bound(const dg_splice_plan_t *plan);
+int dg_splice_plan_run(dg_splice_plan_t *plan, const uint8_t *d_deltas,
+                       const uint64_t *d_offsets, const int32_t *d_seg_status,
+                       const uint64_t *d_src_crc, uint8_t *d_out, uint64_t out_cap,
+                       uint64_t *d_out_offsets, int32_t *d_status, void *stream);
+int dg_splice_plan_set_timing(dg_splice_plan_t *plan, int slots);
+int dg_splice_plan_stage_times(dg_splice_plan_t *plan, float *ms, const char **names, int n);
+void dg_splice_plan_destroy(dg_splice_plan_t *plan);
+
+/* Host buffers in, host buffers out: deltas[j] / delta_len[j] / seg_status[j]
+ * (may be NULL) per segment, src_crc 8 bytes per group, outs[g] malloc'd,
+ * status[g] may be NULL.  Returns DG_OK (per-group failures in status) or the
+ * first failure when status is NULL. */
+int dg_splice_batch(dg_context_t *ctx, const dg_pair_t *wholes, uint32_t n_groups,
+                    const dg_pair_t *segs, const uint32_t *seg_first,
+                    const uint8_t *const *deltas, const size_t *delta_len,
+                    const int32_t *seg_status, const uint8_t *src_crc,
+                    dg_buffer_t *outs, int32_t *status);
+
+/* One large pair in host memory: dg_segment_pairs, upload, R's CRC on the
+ * device, the encode plan over the segments (every algorithm and option of
+ * dg_encode_plan_create), the splice plan, download.  With DG_OPT_INPLACE the
+ * spliced delta is converted on the host, as dg_encode's is.  out->data is
+ * malloc'd.  Cost: with window_bytes > 0 every segment but the
+ * first lies window_bytes off its pair's diagonal, which onepass encodes on one
+ * wave per segment; with window_bytes == 0 the segments lie on their diagonals
+ * and the splice's time per segment is what remains, so smaller segments
+ * (256 KiB) serve a large onepass pair best. */
+int dg_encode_large(dg_context_t *ctx, dg_algorithm_t algo,
+                    const uint8_t *r, size_t r_len, const uint8_t *v, size_t v_len,
+                    const dg_diff_options_t *opts, uint64_t seg_bytes, uint64_t window_bytes,
+                    dg_buffer_t *out);
+
 /* ── range reads: bytes [off, off + len) of a version kept as R and a delta ────
  *
  * What a version store does most: serve a read of part of a version without
