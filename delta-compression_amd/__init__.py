@@ -27,7 +27,9 @@ Names and argument meanings follow the reference's interface for this path:
 * ``read_range(R, delta, off, length)`` / ``ReadPlan`` / ``read_ranges`` — bytes
   [off, off + length) of the version a standard delta makes of R, without
   rebuilding the version (no reference counterpart: the replay of
-  apply.c:229-249, sliced).
+  apply.c:229-249, sliced).  ``ReadPlan.chunk_index`` / ``index_chunked`` index
+  one large delta with the whole GPU (the same index), and ``decode_large(R,
+  delta)`` is ``decode`` as that index plus ``tile_requests`` tiles of V.
 * ``sketch`` / ``SketchPlan`` / ``sketch_batch`` / ``match_sketches`` /
   ``pick_bases`` — which buffer to encode against: min-wise resemblance
   sketches over the encoders' fingerprints and base selection by the exact
@@ -113,6 +115,8 @@ from ._lib import (  # noqa: F401
     encode_large,
     read_range,
     read_ranges,
+    tile_requests,
+    decode_large,
     sketch,
     sketch_batch,
     match_sketches,
@@ -130,7 +134,7 @@ __all__ = [
     "ComposeDesc", "ComposePlan", "compose", "compose_batch",
     "InvertDesc", "InvertPlan", "invert", "invert_batch",
     "SplicePlan", "segment_pairs", "splice", "splice_batch", "sketch_windows", "encode_large",
-    "ReadPlan", "ReadReq", "ReadStream", "read_range", "read_ranges",
+    "ReadPlan", "ReadReq", "ReadStream", "read_range", "read_ranges", "tile_requests", "decode_large",
     "SketchPlan", "sketch", "sketch_batch", "match_sketches", "match_sketches_device", "pick_bases", "SKETCH_BINS", "SKETCH_EMPTY",
     "MATCH_NONE", "MATCH_ALL", "MATCH_NOT_SELF", "MATCH_EARLIER",
     "crc64_xz", "decode", "default_context", "encode", "encode_batch", "encode_pipelined", "info", "lib",

@@ -267,6 +267,13 @@ def _load() -> C.CDLL:
         "dg_read_plan_destroy": (None, [vp]),
         "dg_read_batch": (C.c_int, [vp, C.POINTER(u8p), C.POINTER(sz), C.POINTER(u8p), C.POINTER(sz), u32,
                                     C.POINTER(ReadReq), u32, C.POINTER(Buffer), C.POINTER(i32)]),
+        "dg_read_plan_chunk_index": (C.c_int, [vp, u32]),
+        "dg_read_plan_index_chunked": (C.c_int, [vp, vp, vp, vp, vp, vp]),
+        "dg_read_plan_index_get": (C.c_int, [vp, u32, vp, u64, C.POINTER(u64)]),
+        "dg_read_plan_index_set_timing": (C.c_int, [vp, C.c_int]),
+        "dg_read_plan_index_stage_times": (C.c_int, [vp, C.POINTER(C.c_float), C.POINTER(C.c_char_p), C.c_int]),
+        "dg_tile_requests": (C.c_int, [u32, u32, C.POINTER(ReadReq), u32, C.POINTER(u32)]),
+        "dg_decode_large": (C.c_int, [vp, u8p, sz, u8p, sz, C.c_int, u32, u32, C.POINTER(Buffer)]),
         "dg_sketch": (C.c_int, [u8p, sz, u32, u32, C.POINTER(u64)]),
         "dg_sketch_match": (C.c_int, [C.POINTER(u64), u32, C.POINTER(u64), u32, u32, C.c_int, u32, u32,
                                       C.POINTER(Match)]),
@@ -1085,6 +1092,68 @@ class ReadPlan(_Plan):
         self.ctx.check(lib.dg_read_plan_run(self.handle, d_ref or None, d_delta or None, d_reqs or None, int(n_req),
                                             d_out or None, d_out_len or None, d_status or None, stream or None),
                        "dg_read_plan_run")
+
+    def chunk_index(self, chunk_bytes: int = 0):
+        """Once per plan: fixes the chunk size (a multiple of 4096; 0: the
+        default) and allocates the chunked index pass's work memory."""
+        self.ctx.check(lib.dg_read_plan_chunk_index(self.handle, int(chunk_bytes)), "dg_read_plan_chunk_index")
+
+    def index_chunked(self, d_delta: int, d_stream_status: int = 0, d_delta_offsets: int = 0, d_delta_status: int = 0,
+                      stream: int = 0):
+        """index() with every stream cut into chunks and parsed by many blocks; the same index."""
+        self.ctx.check(lib.dg_read_plan_index_chunked(self.handle, d_delta, d_delta_offsets or None,
+                                                      d_delta_status or None, d_stream_status or None, stream or None),
+                       "dg_read_plan_index_chunked")
+
+    def index_get(self, i: int) -> bytes:
+        """Stream i's index as the last pass left it: the 32-byte head and, for a
+        stream whose status is 0, its entries (for comparing passes; the layout is private)."""
+        need = C.c_uint64(0)
+        rc = lib.dg_read_plan_index_get(self.handle, int(i), None, 0, C.byref(need))
+        if rc != 7:   # DG_ERR_CAPACITY: the size
+            self.ctx.check(rc or 12, "dg_read_plan_index_get")
+        buf = (C.c_uint8 * need.value)()
+        self.ctx.check(lib.dg_read_plan_index_get(self.handle, int(i), buf, need.value, C.byref(need)),
+                       "dg_read_plan_index_get")
+        return bytes(buf[:need.value])
+
+    def set_index_timing(self, slots: int = 1):
+        self.ctx.check(lib.dg_read_plan_index_set_timing(self.handle, int(slots)), "dg_read_plan_index_set_timing")
+
+    def index_stage_times(self) -> dict:
+        """Mean milliseconds of the chunked passes' stages: map, resolve, fill, total."""
+        ms = (C.c_float * 8)()
+        names = (C.c_char_p * 8)()
+        k = lib.dg_read_plan_index_stage_times(self.handle, ms, names, 8)
+        return {names[j].decode(): float(ms[j]) for j in range(k)}
+
+
+def tile_requests(version_size: int, tile_bytes: int = 0) -> List[Tuple[int, int, int]]:
+    """The (off, length, out_off) read requests of stream 0 that tile
+    [0, version_size) (dg_tile_requests): host arithmetic, no GPU."""
+    n = C.c_uint32(0)
+    rc = lib.dg_tile_requests(int(version_size), int(tile_bytes), None, 0, C.byref(n))
+    if rc not in (0, 7):
+        raise DeltaError(rc, "dg_tile_requests")
+    arr = (ReadReq * max(n.value, 1))()
+    rc = lib.dg_tile_requests(int(version_size), int(tile_bytes), arr, n.value, C.byref(n))
+    if rc:
+        raise DeltaError(rc, "dg_tile_requests")
+    return [(arr[j].off, arr[j].len, arr[j].out_off) for j in range(n.value)]
+
+
+def decode_large(R: bytes, delta: bytes, ignore_hash: bool = False, chunk_bytes: int = 0, tile_bytes: int = 0,
+                 ctx: Optional[Context] = None) -> bytes:
+    """decode() of one delta by the whole GPU (dg_decode_large): a chunked
+    index of the stream, then V read as tiles; the same bytes and statuses."""
+    ctx = ctx or default_context()
+    out = Buffer()
+    rc = lib.dg_decode_large(ctx.handle, _u8(R), len(R), _u8(delta), len(delta), int(ignore_hash), int(chunk_bytes),
+                             int(tile_bytes), C.byref(out))
+    res = C.string_at(out.data, out.len) if out.len else b""
+    lib.dg_buffer_free(C.byref(out))
+    ctx.check(rc, "dg_decode_large")
+    return res
 
 
 def read_range(R: bytes, delta: bytes, off: int, length: int) -> bytes:

@@ -7,7 +7,7 @@
  * :50-62) keep working.  All compute runs on the GPU through the C ABI.
  *
  *   delta encode <greedy|onepass|correcting> <ref> <ver> <delta> [options]
- *   delta decode <ref> <delta> <output> [--ignore-hash]
+ *   delta decode <ref> <delta> <output> [--ignore-hash] [--tile-size N [--chunk-size C]]
  *   delta info <delta>
  *   delta inplace <ref> <delta_in> <delta_out> [--policy localmin|constant]
  *   delta compose <delta_ab> <delta_bc> <delta_out> [--ignore-hash]
@@ -25,7 +25,9 @@
  * (on the GPU, as decode does) unless --ignore-hash is given.  pick prints the
  * resemblance score equal/used of the version with every candidate, in argument
  * order, and the candidate to encode against (dg_sketch, dg_sketch_match: host
- * only, no GPU).
+ * only, no GPU).  decode --tile-size N decodes with the whole GPU
+ * (dg_decode_large): a chunked index of the delta (chunks of C bytes), then the
+ * version read as tiles of N bytes; messages and exit codes are decode's.
  */
 #include <errno.h>
 #include <getopt.h>
@@ -97,7 +99,7 @@ static void usage(void)
 	fprintf(stderr,
 	    "Usage:\n"
 	    "  delta encode <algorithm> <ref> <ver> <delta> [options]\n"
-	    "  delta decode <ref> <delta> <output> [--ignore-hash]\n"
+	    "  delta decode <ref> <delta> <output> [--ignore-hash] [--tile-size N [--chunk-size C]]\n"
 	    "  delta info <delta>\n"
 	    "  delta inplace <ref> <delta_in> <delta_out> [--policy P]\n"
 	    "  delta compose <delta_ab> <delta_bc> <delta_out> [--ignore-hash]\n"
@@ -118,8 +120,13 @@ static void usage(void)
 	    "  --segment-size N   encode: cut the version into segments of N bytes (a multiple of 16,\n"
 	    "                     k/M/B suffix ok), encode them as one batch and splice the deltas\n"
 	    "  --segment-window W bytes of the reference before and after a segment's own range\n"
-	    "                     that it may copy from (default N)\n",
-	    DG_SEED_LEN, (unsigned long)DG_TABLE_SIZE, (unsigned long)DG_MAX_TABLE_SIZE);
+	    "                     that it may copy from (default N)\n"
+	    "  --tile-size N      decode: index the delta in chunks and read the version as tiles of N bytes,\n"
+	    "                     one block per tile (0: the default, %u)\n"
+	    "  --chunk-size C     with --tile-size: bytes of the delta per chunk of the index, a multiple\n"
+	    "                     of 4096 (0: the default, %u)\n",
+	    DG_SEED_LEN, (unsigned long)DG_TABLE_SIZE, (unsigned long)DG_MAX_TABLE_SIZE,
+	    (unsigned)DG_TILE_BYTES_DEFAULT, (unsigned)DG_CHUNK_BYTES_DEFAULT);
 	exit(1);
 }
 
@@ -242,9 +249,21 @@ static int cmd_decode(int argc, char **argv)
 {
 	if (argc < 5) usage();
 	const char *ref_path = argv[2], *delta_path = argv[3], *out_path = argv[4];
-	int ignore = 0;
-	for (int a = 5; a < argc; a++)
+	int ignore = 0, tiled = 0, chunked = 0;
+	size_t tile = 0, chunk = 0;
+	for (int a = 5; a < argc; a++) {
 		if (strcmp(argv[a], "--ignore-hash") == 0) ignore = 1;
+		else if (strcmp(argv[a], "--tile-size") == 0 && a + 1 < argc) { tiled = 1; tile = parse_size_suffix(argv[++a]); }
+		else if (strcmp(argv[a], "--chunk-size") == 0 && a + 1 < argc) { chunked = 1; chunk = parse_size_suffix(argv[++a]); }
+	}
+	if (chunked && !tiled) {
+		fprintf(stderr, "delta: --chunk-size needs --tile-size\n");
+		return 1;
+	}
+	if (tile > 0xFFFFFFFFu || chunk > 0xFFFFFFFFu) {
+		fprintf(stderr, "delta: --tile-size and --chunk-size are below 4 GiB\n");
+		return 1;
+	}
 	size_t rl, dl;
 	uint8_t *r = read_file(ref_path, &rl), *d = read_file(delta_path, &dl);
 	dg_delta_info_t inf;
@@ -261,7 +280,8 @@ static int cmd_decode(int argc, char **argv)
 	    memcmp(c, inf.src_crc, 8) != 0)
 		fprintf(stderr, "warning: skipping source CRC check (--ignore-hash)\n");
 	double t0 = now();
-	int rc = dg_decode(ctx, r, rl, d, dl, ignore, &out);
+	int rc = tiled ? dg_decode_large(ctx, r, rl, d, dl, ignore, (uint32_t)chunk, (uint32_t)tile, &out)
+	               : dg_decode(ctx, r, rl, d, dl, ignore, &out);
 	double t1 = now();
 	if (rc == DG_ERR_SRC_CRC) {
 		dg_crc64_xz(ctx, r, rl, c);

@@ -19,6 +19,7 @@
 #include "dg_hostutil.h"
 #include "dg_plan.h"
 #include "dg_read_dev.h"
+#include "dg_read_plan.h"
 
 using namespace dg;
 using namespace dgrd;
@@ -39,7 +40,25 @@ struct dg_read_plan {
 	DevBuf d_streams;
 	DevBuf d_index, d_index_off;   // the streams' indexes (dg_read_dev.h)
 	TimingRing ring;               // kRdEvents events per run
+	std::vector<dg_read_stream_t> streams;   // host copies, for the chunked index pass (dg_index_host.cpp)
+	std::vector<uint64_t> ioff;
+	void* ext = nullptr;           // that pass's state (read_plan_ext)
+	void (*ext_free)(void*) = nullptr;
+	~dg_read_plan() {
+		if (ext && ext_free) ext_free(ext);
+	}
 };
+
+ReadPlanView dg::read_plan_view(dg_read_plan_t* P) {
+	return ReadPlanView{P->ctx, P->n, P->streams.data(), P->ioff.data(), P->d_streams.as<RdStream>(),
+	                    P->d_index.as<uint8_t>(), P->d_index_off.as<uint64_t>()};
+}
+void** dg::read_plan_ext(dg_read_plan_t* P, void (*release)(void*)) {
+	P->ext_free = release;
+	return &P->ext;
+}
+bool dg::read_plan_indexed(const dg_read_plan_t* P) { return P->indexed; }
+void dg::read_plan_set_indexed(dg_read_plan_t* P) { P->indexed = true; }
 
 extern "C" {
 
@@ -93,6 +112,8 @@ int dg_read_plan_create(dg_context_t* ctx, const dg_read_stream_t* streams, uint
 		delete P;
 		return ctx_fail(ctx, DG_ERR_HIP, "read plan: descriptor upload failed");
 	}
+	P->streams.assign(streams, streams + n);
+	P->ioff = std::move(ioff);
 	*out = P;
 	return DG_OK;
 }

@@ -1211,6 +1211,90 @@ int dg_read_batch(dg_context_t *ctx, const uint8_t *const *refs, const size_t *r
                   const dg_read_req_t *reqs /* host */, uint32_t n_req,
                   dg_buffer_t *outs, int32_t *status);
 
+/* ── a chunked index: one stream parsed by many blocks ───────────────────────
+ *
+ * dg_read_plan_index gives every stream to one block, which suits a batch of
+ * many streams.  One large delta (dg_encode_large's of a 1 GiB pair is about
+ * 220 MB) is instead indexed by the whole GPU: every stream of the plan is cut
+ * into chunks of chunk_bytes (a stream shorter than one chunk is one chunk),
+ * and the pass is four launches on one stream ("A chunked index"):
+ * per chunk, for EVERY offset of the chunk, where the chain that starts there
+ * leaves the chunk; one walk over the chunks that picks the true chain; per
+ * chunk the real validation from its true entry, which writes the index.
+ *
+ * dg_read_plan_chunk_index is called once per plan (a second call is
+ * DG_ERR_INVALID_ARG).  chunk_bytes is a multiple of 4096, at least 4096, or 0
+ * for DG_CHUNK_BYTES_DEFAULT; anything else is DG_ERR_INVALID_ARG.  It
+ * allocates all work memory of the pass, so a pass allocates nothing:
+ *     4 bytes per stream byte (of the plan's delta_len bounds)
+ *   + 24 bytes per chunk (sum over streams of max(1, ceil(delta_len / chunk_bytes)))
+ *   + 32 bytes and two table words (12 bytes) per stream;
+ * DG_ERR_NOMEM when it cannot be had.  A stream bound above 4 GiB - 16 bytes is
+ * DG_ERR_TOO_LARGE (the pass keeps stream offsets and two codes in a u32).  The
+ * kernels live in dg_index.hsaco beside libdeltagpu.so and are loaded here;
+ * DG_ERR_HIP with the path in dg_last_error when it is missing.
+ *
+ * dg_read_plan_index_chunked takes dg_read_plan_index's arguments with the same
+ * meanings (offsets array, passed-on status, DG_ERR_CAPACITY for a stream longer
+ * than the plan allows, d_stream_status) and leaves the plan in exactly the
+ * state dg_read_plan_index would: every stream's head is identical (status,
+ * version_size, the sequential flag, the entry count, where the stream was and
+ * its length) and, for every stream whose status is 0, so is every entry.  A
+ * failed stream's entries are unspecified in both passes.  dg_read_plan_run
+ * does not know which pass ran.  Before dg_read_plan_chunk_index it is
+ * DG_ERR_INVALID_ARG (dg_last_error says so).  Asynchronous on the caller's
+ * stream, no host synchronisation, no allocation: it chains after
+ * dg_encode_plan_run and dg_splice_plan_run as the one-block pass does.  The
+ * grid is sized from the plan's delta_len bounds; with device-side offsets the
+ * blocks past a stream's real length leave at once.  No block waits for
+ * another inside a kernel.
+ *
+ * dg_read_plan_index_get copies stream stream_i's 32-byte head and, when its
+ * status is 0, its entries (8 bytes each, the head's entry count of them) to
+ * host memory, after synchronising the context's stream.  *bytes is set to the
+ * bytes needed; a smaller cap is DG_ERR_CAPACITY.  DG_ERR_INVALID_ARG before
+ * any index pass.  It exists so that two index passes can be compared, and for
+ * diagnostics: the layout stays private.
+ *
+ * Stage timing of the chunked passes: dg_read_plan_index_set_timing, then
+ * dg_read_plan_index_stage_times: "map", "resolve", "fill" (with the launch
+ * that writes the heads), "total".  dg_read_plan_stage_times is unchanged. */
+#define DG_CHUNK_BYTES_DEFAULT 65536u
+int dg_read_plan_chunk_index(dg_read_plan_t *plan, uint32_t chunk_bytes);
+int dg_read_plan_index_chunked(dg_read_plan_t *plan, const uint8_t *d_delta,
+                               const uint64_t *d_delta_offsets, const int32_t *d_delta_status,
+                               int32_t *d_stream_status, void *stream);
+int dg_read_plan_index_get(dg_read_plan_t *plan, uint32_t stream_i,
+                           void *host_dst, uint64_t cap, uint64_t *bytes);
+int dg_read_plan_index_set_timing(dg_read_plan_t *plan, int slots);
+int dg_read_plan_index_stage_times(dg_read_plan_t *plan, float *ms, const char **names, int n);
+
+/* ── one delta decoded by the whole GPU ──────────────────────────────────────
+ *
+ * dg_tile_requests is host arithmetic (no GPU, no context): the read requests
+ * of stream 0 that tile [0, version_size) in tiles of tile_bytes (0:
+ * DG_TILE_BYTES_DEFAULT), slots contiguous (out_off == off), the last tile
+ * short.  *n takes their number, ceil(version_size / tile_bytes) (0 for
+ * version_size 0); a smaller cap is DG_ERR_CAPACITY and writes nothing else.
+ *
+ * dg_decode_large gives, for every input, the status and the output bytes that
+ * dg_decode gives (the output on DG_ERR_DST_CRC and the malformed / source /
+ * output precedence included).  Route: the header checks on the host; an
+ * in-place delta, or an r_len or delta_len of 4 GiB or more, goes to dg_decode;
+ * otherwise upload, a one-stream read plan, the chunked index (chunk_bytes as
+ * above); a failing stream status is DG_ERR_MALFORMED; a valid stream that is
+ * not sequential goes to dg_decode_batch_device on the bytes already uploaded
+ * (the read kernel would replay the whole stream once per tile); a sequential
+ * stream is read as dg_tile_requests tiles into one buffer, the CRCs of R and
+ * of the output (dg_crc64_xz_batch_device) are compared with the header unless
+ * ignore_hash, and the output is downloaded. */
+#define DG_TILE_BYTES_DEFAULT 65536u
+int dg_tile_requests(uint32_t version_size, uint32_t tile_bytes,
+                     dg_read_req_t *reqs, uint32_t cap, uint32_t *n);
+int dg_decode_large(dg_context_t *ctx, const uint8_t *r, size_t r_len,
+                    const uint8_t *delta, size_t delta_len, int ignore_hash,
+                    uint32_t chunk_bytes, uint32_t tile_bytes, dg_buffer_t *out);
+
 /* ── reference selection: resemblance sketches and base matching ─────────────
  *
  * Every entry point above starts from a pair: the caller knows which R a V is
