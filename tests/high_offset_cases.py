@@ -1,0 +1,513 @@
+"""Command streams whose offsets and sizes sit in the upper half of the u32
+range, for tests/test_high_offset_cpu.py and tests/test_gpu_high_offset.py.
+
+The transforms are pure functions of the command streams, and a stream of 60
+bytes can describe a 4 GiB version, so nothing here is large: the streams are
+built with struct.pack, the one reference R is a SparseBytes, and every expected
+result comes from tests/sparse_model.py (pinned to the dense models by
+tests/test_sparse_model_cpu.py).  Nothing here needs a GPU or the library.
+
+E = {2^31 - 1, 2^31, 2^31 + 1, 2^32 - 2, 2^32 - 1}.  Every operator's cases put
+each of src, dst, src + len, dst + len, version_size and ref_len on every member
+of E that its limits allow; reach() computes what the accepted cases reach and
+ALLOWED states what they must (tests/test_high_offset_cpu.py compares the two,
+so a family that silently shrinks fails).  What a limit excludes:
+
+  * R is RLEN = 2^32 - 1 - 2^20 bytes, the largest reference the encode and
+    splice plans accept (tests/test_plan_cpu.py, tests/test_splice_cpu.py), so
+    wherever a stream is checked against R (read, decode, update, invert) src,
+    src + len and ref_len reach 2^31 - 1, 2^31 and 2^31 + 1 only: 2^32 - 2 and
+    2^32 - 1 are past R's end.
+  * splice: whole.r_len and whole.v_len are below 2^32 - 2^20, so every
+    quantity of a spliced delta reaches the three low members only.
+  * compose never sees R: it has no ref_len.  A's src + len may reach 2^32
+    itself (the contract refuses "> 2^32" only), which is pinned as accepted.
+  * decode and update: versions stay below 64 KiB (one block moves and, with CRC
+    checks on, checksums a whole stream, and R's CRC over 4 GiB by one block
+    would take seconds: these cases run with ignore_hash), so dst, dst + len and
+    version_size are small; only src, src + len and ref_len are high.
+
+No case asks a one-block kernel to move more than 1 MiB: outputs of compose,
+invert and splice carry a few KiB of literals, every read request is at most
+1 MiB after clipping (checked when the corpus is built).
+"""
+from __future__ import annotations
+
+import random
+import struct
+
+import sparse_model as sm
+
+OK, UNSUPPORTED, TOO_LARGE, MALFORMED = sm.OK, sm.UNSUPPORTED, sm.TOO_LARGE, sm.MALFORMED
+H = 1 << 31
+U32 = 1 << 32
+E = [H - 1, H, H + 1, U32 - 2, U32 - 1]
+LOW = E[:3]
+RLEN = U32 - 1 - (1 << 20)
+WINDOW_BYTES = 64
+EDGES = [1024, 4096, 65536]            # index stride / one-wave parse window, decode's window and the chunk, a large chunk
+QUANTITIES = ["src", "dst", "src+len", "dst+len", "version_size", "ref_len"]
+CRC_R, CRC_1, CRC_2 = b"R-crc64.", b"V1crc64.", b"V2crc64."   # nothing checks them: these cases run without CRC checks
+
+ALLOWED = {
+    "compose": {"src": E, "dst": E, "src+len": E + [U32], "dst+len": E, "version_size": E, "ref_len": []},
+    "invert": {"src": LOW, "dst": E, "src+len": LOW, "dst+len": E, "version_size": E, "ref_len": LOW},
+    "read": {"src": LOW, "dst": E, "src+len": LOW, "dst+len": E, "version_size": E, "ref_len": LOW},
+    "splice": {"src": LOW, "dst": LOW, "src+len": LOW, "dst+len": LOW, "version_size": LOW, "ref_len": LOW},
+    "decode": {"src": LOW, "dst": [], "src+len": LOW, "dst+len": [], "version_size": [], "ref_len": LOW},
+    "update": {"src": LOW, "dst": [], "src+len": LOW, "dst+len": [], "version_size": [], "ref_len": LOW},
+}
+
+
+# ── the one reference ──
+
+def _reference():
+    rng = random.Random(0x2331)
+    at = [12345, H // 2 + 7, H - 33, H + 100001, 3 * (1 << 30) + 5, RLEN - WINDOW_BYTES]
+    assert all(o % 2 for o in at) and at[2] <= H - 1 and H + 1 < at[2] + WINDOW_BYTES and at[-1] + WINDOW_BYTES == RLEN
+    return sm.SparseBytes(RLEN, {o: rng.randbytes(WINDOW_BYTES) for o in at})
+
+
+R = _reference()
+
+
+# ── streams ──
+
+def seq(cmds, at=0):
+    """("C", src, len) / ("A", bytes) placed one after the other from `at`: (placed, end)."""
+    out = []
+    for c in cmds:
+        if c[0] == "C":
+            out.append(("C", c[1], at, c[2]))
+            at += c[2]
+        else:
+            out.append(("A", at, bytes(c[1])))
+            at += len(c[1])
+    return out, at
+
+
+def stream(placed, version_size, *, src_crc=CRC_R, dst_crc=CRC_1, flags=0, end=True):
+    """placed: ("C", src, dst, len) / ("A", dst, bytes) in stream order; fields are taken mod 2^32."""
+    out = bytearray(b"DLT\x03" + bytes([flags]) + struct.pack(">I", version_size % U32) + src_crc + dst_crc)
+    for c in placed:
+        if c[0] == "C":
+            out += b"\x01" + struct.pack(">III", c[1] % U32, c[2] % U32, c[3] % U32)
+        else:
+            out += b"\x02" + struct.pack(">II", c[1] % U32, len(c[2]) % U32) + c[2]
+    return bytes(out + (b"\x00" if end else b""))
+
+
+def sstream(cmds, **kw):
+    placed, size = seq(cmds)
+    return stream(placed, size, **kw)
+
+
+def edges_full(rng):
+    """A version of 2^32 - 1 bytes whose command boundaries are every member of E,
+    closed by a zero-length COPY at dst = 0xFFFFFFFF (the value the index keeps
+    for "after the last command").  Sources stay inside R."""
+    cmds = [("C", 1, H - 1), ("A", rng.randbytes(1)), ("C", H, 1), ("A", rng.randbytes(1)), ("C", 5, U32 - 2 - (H + 2)),
+            ("A", rng.randbytes(1)), ("C", 7, 0)]
+    placed, size = seq(cmds)
+    assert size == U32 - 1 and [c[1 if c[0] == "A" else 2] for c in placed] == [0, H - 1, H, H + 1, H + 2, U32 - 2, U32 - 1]
+    return placed, size
+
+
+def covering(rng, ref_len, target=None, n_small=420):
+    """A sequentially placed stream that reads nearly all of R[0, ref_len): what
+    invert needs to keep its literals small, and a fair stream for every other
+    operator.  One COPY up to V offset 2^31 exactly; then n_small short commands,
+    all with dst >= 2^31, COPYs of 3..9 bytes whose sources run on from 2^31 in
+    shuffled order with gaps of 0..3 bytes, an ADD after some; then one COPY to
+    one byte before R's end.  With target, the first command at dst 2^31 starts at
+    that stream offset: 1-byte COPYs of consecutive sources (which merge) and one
+    ADD pad the stream in front of the long COPY.  n_small = 1000 makes a stream
+    of more than three 4 KiB chunks."""
+    n_pad, fine = 0, 3
+    if target is not None:
+        n_pad = (target - 47 - 1) // 13
+        fine = target - 47 - 13 * n_pad
+        assert 1 <= fine <= 13
+    cmds = [("C", k, 1) for k in range(n_pad)] + [("A", rng.randbytes(fine)), ("C", n_pad, H - n_pad - fine)]
+    at_r = H - fine                      # R is read up to here
+    small = []
+    for k in range(n_small):
+        at_r += rng.randint(0, 3) if k % 5 else 0
+        n = rng.randint(3, 9)
+        small.append(("C", at_r, n))
+        at_r += n
+    rng.shuffle(small)
+    body = []
+    for k, c in enumerate(small):
+        body.append(c)
+        if k % 9 == 4:
+            body.append(("A", rng.randbytes(rng.randint(1, 4))))
+    cmds += body + [("C", at_r, ref_len - 1 - at_r)]
+    placed, size = seq(cmds)
+    d = stream(placed, size)
+    if target is not None:
+        first_high = next(k for k, c in enumerate(placed) if c[1 if c[0] == "A" else 2] >= H)
+        assert len(stream(placed[:first_high], 0, end=False)) == target and placed[first_high][2] == H
+    assert size < U32 and at_r < ref_len - 1
+    return d, placed, size
+
+
+def edge_targets():
+    """Stream offsets 4 bytes before each boundary, counted from the stream's start
+    (chunks, index stride) and from byte 25 (the parse windows)."""
+    return [w - 4 + b for w in EDGES for b in (0, 25)]
+
+
+# ── compose: (name, A, B, status) ──
+
+def compose_cases():
+    rng = random.Random(0x2332)
+    out = []
+
+    def add(name, a, b, status=OK):
+        a = a if isinstance(a, bytes) else sstream(a, src_crc=CRC_R, dst_crc=CRC_1)
+        b = b if isinstance(b, bytes) else sstream(b, src_crc=CRC_1, dst_crc=CRC_2)
+        out.append((name, a, b, status))
+
+    # long single commands: one COPY of A that ends at R offset 2^32 itself, read whole by B
+    for e in E:
+        add(f"long_copy_{e:#x}", [("C", U32 - e, e)], [("C", 0, e)])
+    add("long_copy_src_fffffffe", [("C", U32 - 2, 2)], [("C", 1, 1), ("C", 0, 2)])
+    add("long_copy_src_ffffffff", [("A", b"ab"), ("C", U32 - 1, 1)], [("C", 2, 1), ("C", 0, 3)])
+    # B copies whole, from 1 and from a piece boundary a version whose boundaries are all of E
+    pf, size = edges_full(rng)
+    af = stream(pf, size, src_crc=CRC_R, dst_crc=CRC_1)
+    add("edges_whole", af, [("C", 0, U32 - 1)])
+    add("edges_from_1", af, [("C", 1, U32 - 2)])
+    add("edges_from_boundary", af, [("A", b"x"), ("C", H - 1, H), ("C", 0, H - 2)])
+    add("edges_across_each", af, [("C", e - 1, 2) for e in E[:4]] + [("C", e, 1) for e in E[:4]] + [("C", H - 2, 5)])
+    # merges: pieces below 2^31 each, above it together: inside A, across commands of B, across both
+    add("merge_inside_a", [("C", 0, H - 1), ("C", H - 1, 2), ("C", H + 1, H - 3)], [("C", 0, U32 - 2)])
+    add("merge_across_b", [("C", 9, U32 - 10)], [("C", 0, H - 1), ("C", H - 1, 1), ("C", H, H - 10)])
+    add("merge_across_both", [("C", 1, H - 1), ("C", H, H - 1)], [("C", 1, H - 2), ("C", H - 1, H - 2)])
+    add("no_merge_gap_of_one", [("C", 1, H - 1), ("C", H + 1, H - 2)], [("C", 0, U32 - 3)])
+    # table searches: 400 and more commands in both streams, A's pieces on both sides of V1 offset 2^31,
+    # B's COPYs inside, at and across them, every dst of B's short commands above 2^31
+    a_cmds = [("C", 7, H - 600)]
+    for k in range(420):
+        a_cmds.append(("A", rng.randbytes(rng.randint(1, 3))) if k % 4 == 3 else ("C", rng.randrange(H - 99, H + 99), rng.randint(2, 6)))
+    a_cmds.append(("C", H + 500, 4000))
+    pa, va = seq(a_cmds)
+    bounds = [c[1 if c[0] == "A" else 2] for c in pa[1:]]
+    assert bounds[0] < H < bounds[-1] and va > H + 600
+    b_cmds = [("C", 0, H)]
+    for k, x in enumerate(bounds):
+        n = pa[1 + k][3] if pa[1 + k][0] == "C" else len(pa[1 + k][2])
+        b_cmds.append([("C", x - 2, 4), ("C", x, n), ("C", x + 1, 1), ("C", x - 3, 3)][k % 4])
+        if k % 50 == 49:
+            b_cmds.append(("A", rng.randbytes(2)))
+    add("table_search", a_cmds, b_cmds)
+    assert len(a_cmds) >= 400 and len(b_cmds) >= 400
+    # window and chunk edges: the first command at dst 2^31 four bytes before a boundary, as A and as B
+    for t in edge_targets():
+        d, _, vs = covering(rng, RLEN, target=t, n_small=1000)
+        add(f"edge_{t}_as_a", d, [("C", H - 40, 90), ("C", 0, vs)])
+        add(f"edge_{t}_as_b", [("C", 3, RLEN)], d[:9] + CRC_1 + CRC_2 + d[25:])
+    # refusals by wrap, each the only defect of its pair
+    add("a_src_len_2p32_plus_16", stream([("C", U32 - 1, 0, 17)], 17), [("C", 0, 17)], MALFORMED)
+    for e in E:
+        add(f"b_src_len_past_v1_{e:#x}", [("C", 0, e)], stream([("C", 1, 0, e)], e, src_crc=CRC_1, dst_crc=CRC_2), MALFORMED)
+    add("b_src_len_2p32_plus_16", [("C", 0, U32 - 1)], stream([("C", U32 - 1, 0, 17)], 17, src_crc=CRC_1, dst_crc=CRC_2), MALFORMED)
+    two = [("C", 0, 0, H), ("C", H, H, H)]
+    add("a_sum_2p32_version_size_0", stream(two, 0), stream([], 0, src_crc=CRC_1, dst_crc=CRC_2), UNSUPPORTED)
+    add("a_sum_2p32_plus_16", stream(two + [("C", 0, U32, 16)], 16), [("C", 0, 16)], UNSUPPORTED)
+    add("b_sum_2p32_plus_16", [("C", 0, U32 - 1)],
+        stream([("C", 0, 0, H), ("C", 0, H, H), ("C", 0, U32, 16)], 16, src_crc=CRC_1, dst_crc=CRC_2), UNSUPPORTED)
+    add("a_add_dst_len_wraps", stream([("C", 0, 0, U32 - 8), ("A", U32 - 8, rng.randbytes(24))], 16), [("C", 0, 16)], UNSUPPORTED)
+    return out
+
+
+# ── invert: (name, ref_len, A, status), against R.head(ref_len) ──
+
+def invert_cases():
+    rng = random.Random(0x2333)
+    out = []
+
+    def add(name, ref_len, a, status=OK):
+        out.append((name, ref_len, a if isinstance(a, bytes) else sstream(a), status))
+
+    for e in LOW:
+        add(f"long_copy_ref_{e:#x}", e, [("C", 0, e)])
+        add(f"tail_copy_ref_{e:#x}", e, [("C", e - 1, 1), ("C", 0, e - 1)])
+    add("long_copy_whole_r", RLEN, [("C", 3, RLEN - 5)])
+    # V of 2^32 - 1 bytes: the second COPY is shadowed by the first and vanishes; dst and dst + len on 2^32 - 2 and 2^32 - 1
+    add("version_ffffffff", RLEN, [("C", 0, RLEN), ("C", 5, (1 << 20) - 1), ("A", b"z"), ("C", 9, 0)])
+    # command boundaries of V on every member of E, R covered up to its last byte (the fifth COPY is shadowed)
+    add("version_fffffffe", RLEN, [("C", 0, RLEN), ("C", 5, U32 - 2 - RLEN)])
+    add("edges", RLEN, [("C", 0, H - 1), ("A", b"p"), ("C", H - 1, 1), ("A", b"q"), ("C", H, RLEN - H - 1),
+                        ("C", 0, U32 - 2 - (RLEN + 1)), ("A", b"r"), ("C", 7, 0)])
+    # keys on both sides of 2^31, not in key order: a signed compare would put the high ones first
+    add("unsorted_across_2p31", RLEN, [("C", H + 1, RLEN - H - 1), ("C", H, 1), ("C", H - 1, 1), ("C", 0, H - 1)])
+    add("unsorted_equal_src", H + 1, [("C", H - 1, 1), ("C", H - 1, 2), ("C", 0, H - 1)])
+    # merges: two COPYs below 2^31 each whose inverse is one COPY above it; and the same with a gap in V
+    add("merge", RLEN, [("C", 0, H - 1), ("C", H - 1, RLEN - 3 - (H - 1))])
+    add("no_merge_dst_gap", RLEN, [("C", 0, H - 1), ("A", b"q"), ("C", H - 1, RLEN - 3 - (H - 1))])
+    # table searches and window edges
+    add("table_search", RLEN, covering(rng, RLEN, n_small=520)[0])
+    add("table_search_ref_2p31_plus_4000", H + 4000, covering(rng, H + 4000)[0])
+    for t in edge_targets():
+        add(f"edge_{t}", RLEN, covering(rng, RLEN, target=t, n_small=1000)[0])
+    # refusals
+    for e in LOW:
+        add(f"src_len_past_ref_{e:#x}", e, stream([("C", 0, 0, e - 1), ("C", e - 1, e - 1, 2)], e + 1), MALFORMED)
+    add("src_len_2p32", RLEN, stream([("C", U32 - 16, 0, 16)], 16), MALFORMED)
+    add("src_len_2p32_plus_16", RLEN, stream([("C", U32 - 16, 0, 32)], 32), MALFORMED)
+    two = [("C", 0, 0, H), ("C", 5, H, H)]
+    add("sum_2p32_version_size_0", RLEN, stream(two, 0), UNSUPPORTED)
+    add("sum_2p32_plus_16", RLEN, stream(two + [("C", 0, U32, 16)], 16), UNSUPPORTED)
+    add("add_dst_len_wraps", RLEN,
+        stream([("C", 0, 0, RLEN), ("C", 0, RLEN, U32 - 8 - RLEN), ("A", U32 - 8, rng.randbytes(24))], 16), UNSUPPORTED)
+    return out
+
+
+# ── read: (name, ref_len, delta, status, [(off, len)]) ──
+
+def _requests(d, ref_len):
+    st = sm.Stream.of(d)
+    vs = st.version_size
+    high = [c[2] for c in st.cmds if c[2] >= H]
+    picked = high[:10] + high[-10:] + high[len(high) // 2:len(high) // 2 + 4]
+    seen, rs = set(), []
+    for b in picked:
+        if b not in seen:
+            seen.add(b)
+            rs += [(max(o, 0), n) for o, n in ((b - 1, 2), (b, 1), (b, 15), (b, 16), (b, 17), (b - 17, 34))]
+    rs += [(e, 40) for e in E] + [(e - 40, 81) for e in E]
+    rs += [(vs, 5), (max(vs - 1, 0), 1), (max(vs - 3, 0), 10), (max(vs - 100, 0), 0xFFFFFFFF), (U32 - 5, 100), (U32 - 1, 1),
+           (0xFFFFFFFF, 0xFFFFFFFF), (0, 0), (0, 64), (H - 4096, 8192)]
+    for off, n in rs:   # the condition of the module docstring
+        assert (0 if off >= vs else min(n, vs - off)) <= sm.SLICE_MAX
+    return rs
+
+
+def read_cases():
+    rng = random.Random(0x2334)
+    out = []
+
+    def add(name, ref_len, d, status=OK):
+        d = d if isinstance(d, bytes) else sstream(d)
+        out.append((name, ref_len, d, status, _requests(d, ref_len) if status == OK else [(0, 16), (H, 1), (0, 0)]))
+
+    pf, size = edges_full(rng)
+    add("edges", RLEN, stream(pf, size))
+    add("edges_add_at_ffffffff", RLEN, stream(pf[:-1] + [("A", U32 - 1, b"")], size))
+    add("edges_descending", RLEN, stream(pf[::-1], size))              # not sequential: the whole-stream path
+    add("edges_exchanged", RLEN, stream([pf[1], pf[0]] + pf[2:], size))
+    for e in E:   # version_size on every member; the last byte an ADD
+        add(f"version_{e:#x}", RLEN, [("C", 3, H - 2), ("C", 3, e - 1 - (H - 2)), ("A", rng.randbytes(1))])
+    for e in LOW:
+        add(f"ref_len_{e:#x}", e, [("A", rng.randbytes(2)), ("C", e - 40, 40), ("C", 0, e), ("C", e - 1, 1)])
+    add("long_copy_from_window", RLEN, [("C", 3, H + 9), ("A", rng.randbytes(5)), ("C", H - 33, 100), ("C", H + 1, 7), ("C", H - 1, 2)])
+    add("gap_above_2p31", RLEN, stream([("C", 0, 0, H - 10), ("A", H + 10, rng.randbytes(7)), ("C", H - 33, H + 100, 64)], U32 - 1))
+    add("overwrite_above_2p31", RLEN, stream([("C", 4, 0, RLEN - 4), ("A", H - 2, rng.randbytes(5)), ("C", RLEN - 64, H, 64)], U32 - 2))
+    add("table_search", RLEN, covering(rng, RLEN)[0])
+    for t in edge_targets():
+        add(f"edge_{t}", RLEN, covering(rng, RLEN, target=t, n_small=1000)[0])
+    # refusals, each the only defect of its stream
+    for e in LOW:
+        add(f"src_len_past_ref_{e:#x}", e, stream([("C", e - 1, 0, 2)], 2), MALFORMED)
+    add("src_len_2p32", RLEN, stream([("C", U32 - 16, 0, 16)], 16), MALFORMED)
+    add("src_len_2p32_plus_16", RLEN, stream([("C", U32 - 16, 0, 32)], 32), MALFORMED)
+    for e in E:
+        add(f"dst_len_past_version_{e:#x}", RLEN, stream([("C", 0, e - 1, 2)], e), MALFORMED)
+    add("dst_len_2p32", RLEN, stream([("C", 0, U32 - 16, 16)], U32 - 1), MALFORMED)
+    add("dst_len_2p32_plus_16", RLEN, stream([("C", 0, U32 - 16, 32)], U32 - 1), MALFORMED)
+    add("add_dst_len_wraps", RLEN, stream([("A", U32 - 8, rng.randbytes(24))], U32 - 1), MALFORMED)
+    return out
+
+
+# ── splice: (name, whole, segments, deltas, src_crc, status) ──
+
+def _tile(v_len, n):
+    cuts = [v_len * k // n for k in range(n + 1)]
+    return [(a, b - a) for a, b in zip(cuts[:-1], cuts[1:])]
+
+
+def splice_cases():
+    rng = random.Random(0x2335)
+    out = []
+
+    def seg_stream(cmds, **kw):
+        return sstream(cmds, src_crc=rng.randbytes(8), dst_crc=rng.randbytes(8), **kw)
+
+    def add(name, whole, segs, deltas, status=OK):
+        out.append((name, whole, segs, deltas, rng.randbytes(8), status))
+
+    top = sm.PLAN_LIMIT - 1   # == RLEN: the largest r_len and v_len
+    # geometry: 1, 2, 64 and 65 segments that tile a V just under the limit; every segment one COPY of its own
+    # span of R through a window that is all of R, so the splice is one COPY through every seam: pieces below 2^31
+    # each (from 2 segments on), 2^32 - 2^20 - 1 together; the CRC weights cover |Y| up to about 4 GiB
+    for n in (1, 2, 64, 65):
+        segs = [(16, top, 48 + a, b) for a, b in _tile(top, n)]
+        add(f"one_copy_{n}", (16, top, 48, top), segs, [seg_stream([("C", a - 48, b)]) for _, _, a, b in segs])
+    # the same through empty segments, and with a literal at one seam
+    cuts = [0, 0, H - 1, H - 1, H - 1, H, H + 1, top, top]
+    segs = [(0, top, a, b - a) for a, b in zip(cuts[:-1], cuts[1:])]
+    add("one_copy_through_empty_segments", (0, top, 0, top), segs,
+        [seg_stream([("C", a, b)] if b else []) for _, _, a, b in segs])
+    deltas = [seg_stream([("C", a, b - 1), ("A", b"!")] if k == 1 else [("C", a, b)] if b else [])
+              for k, (_, _, a, b) in enumerate(segs)]
+    add("literal_at_seam_2p31", (0, top, 0, top), segs, deltas)
+    # windows whose offset in R rebases a src across 2^31; neighbours that merge after rebasing and ones that do not
+    segs = [(H - 10, 100, 0, 30), (H + 20, 1000, 30, 70), (H - 1, 2, 100, 2), (0, top, 102, H + 1 - 102), (H + 1, 7, H + 1, 6)]
+    deltas = [seg_stream([("A", b"ab"), ("C", 2, 28)]), seg_stream([("C", 0, 60), ("C", 70, 10)]), seg_stream([("C", 0, 2)]),
+              seg_stream([("C", 3, H + 1 - 102)]), seg_stream([("C", 1, 6)])]
+    add("rebase_across_2p31", (0, top, 0, H + 7), segs, deltas)
+    for e in LOW:   # whole.r_len, whole.v_len, a rebased src + len and dst + len on e
+        segs = [(5, e - 5, 0, e - 7), (e - 2, 2, e - 7, 7)]
+        add(f"ends_at_{e:#x}", (0, e, 0, e), segs, [seg_stream([("C", 0, e - 7)]), seg_stream([("A", b"12345"), ("C", 0, 2)])])
+        segs = [(0, e + 9, 0, e), (e, 9, e, 4)]   # a rebased src and a dst on e; the seam's COPYs merge
+        add(f"starts_at_{e:#x}", (0, e + 9, 0, e + 4), segs, [seg_stream([("A", b"xy"), ("C", 2, e - 2)]), seg_stream([("C", 0, 4)])])
+    # 400 and more commands in one segment whose window starts at 2^31 - 600: every rebased src near or above 2^31
+    cmds = []
+    for k in range(430):
+        cmds.append(("A", rng.randbytes(rng.randint(1, 3))) if k % 4 == 3 else ("C", rng.randrange(500, 700), rng.randint(2, 6)))
+    _, n0 = seq(cmds)
+    segs = [(0, top, 0, H - 7), (H - 600, 2000, H - 7, n0), (H + 100001, 64, H - 7 + n0, 64)]
+    add("table_search_in_a_window", (0, top, 0, H - 7 + n0 + 64), segs,
+        [seg_stream([("C", 0, H - 7)]), seg_stream(cmds), seg_stream([("C", 0, 64)])])
+    for t in edge_targets()[:4]:   # the 1 KiB and 4 KiB edges (one wave parses a segment: no chunks)
+        d, _, vs = covering(rng, RLEN, target=t, n_small=1000)
+        add(f"edge_{t}", (0, top, 0, vs + 5), [(0, top, 0, vs), (RLEN - 64, 64, vs, 5)], [d, seg_stream([("C", 59, 5)])])
+    # refusals: the bound of a segment's COPY is its window, seg[j].r_len
+    for e in LOW:
+        add(f"src_len_past_window_{e:#x}", (0, top, 0, 10), [(0, 50, 0, 4), (7, e, 4, 6)],
+            [seg_stream([("C", 0, 4)]), seg_stream([("C", e - 5, 6)])], MALFORMED)
+    add("src_len_2p32", (0, top, 0, 16), [(0, top, 0, 16)], [stream([("C", U32 - 16, 0, 16)], 16)], MALFORMED)
+    add("src_len_2p32_plus_16", (0, top, 0, 32), [(0, top, 0, 32)], [stream([("C", U32 - 16, 0, 32)], 32)], MALFORMED)
+    two = [("C", 0, 0, H), ("C", 5, H, H)]
+    add("sum_2p32_version_size_0", (0, top, 0, 4), [(0, top, 0, 0), (0, 9, 0, 4)],
+        [stream(two, 0), seg_stream([("C", 1, 4)])], UNSUPPORTED)
+    add("sum_2p32_plus_16", (0, top, 0, 16), [(0, top, 0, 16)], [stream(two + [("C", 0, U32, 16)], 16)], UNSUPPORTED)
+    add("add_dst_len_wraps", (0, top, 0, 16), [(0, top, 0, 16)],
+        [stream([("C", 0, 0, RLEN), ("C", 0, RLEN, U32 - 8 - RLEN), ("A", U32 - 8, rng.randbytes(24))], 16)], UNSUPPORTED)
+    add("r_len_at_the_limit", (0, top + 1, 0, 4), [(0, 9, 0, 4)], [seg_stream([("C", 1, 4)])], TOO_LARGE)
+    add("v_len_at_the_limit", (0, top, 0, top + 1), [(0, top, 0, top + 1)], [seg_stream([("C", 0, top + 1)])], TOO_LARGE)
+    return out
+
+
+# ── decode and update: (name, ref_len, delta, status); versions of at most 64 KiB from R's windows above 2^31 ──
+
+def _window_copies(ref_len):
+    """(src, len) inside R's windows, with src and src + len on what fits of E."""
+    picks = [(H - 33, 32), (H - 2, 1), (H - 1, 1), (H - 1, 2), (H, 1), (H + 1, 20), (H - 20, 40), (H + 100001, 64),
+             (3 * (1 << 30) + 5, 64), (RLEN - 64, 64), (RLEN - 1, 1)]
+    return [(s, n) for s, n in picks if s + n <= ref_len]
+
+
+def decode_cases():
+    rng = random.Random(0x2336)
+    out = []
+    for ref_len in LOW + [RLEN]:
+        cmds = []
+        for s, n in _window_copies(ref_len):
+            cmds += [("C", s, n), ("A", rng.randbytes(rng.randint(1, 17)))]
+        cmds.append(("C", ref_len - 9, 9))                       # src + len == ref_len
+        out.append((f"windows_ref_{ref_len:#x}", ref_len, sstream(cmds), OK))
+    cmds = []
+    for k in range(1200):   # more than three 4 KiB windows of commands, every src in a window of R around or above 2^31
+        cmds.append(("A", rng.randbytes(rng.randint(1, 9))) if k % 3 == 2 else
+                    ("C", rng.choice([H - 33, H + 100001, RLEN - 64]) + rng.randrange(0, 40), rng.randint(1, 24)))
+    out.append(("three_windows", RLEN, sstream(cmds), OK))
+    assert len(out[-1][2]) > 3 * 4096
+    placed, size = seq(cmds[:60])
+    out.append(("gap_and_overwrite", RLEN, stream(placed[::-1] + [("C", RLEN - 64, 10, 64)], size + 100), OK))
+    for e in LOW:
+        out.append((f"src_len_past_ref_{e:#x}", e, stream([("C", H - 33, 0, 8), ("C", e - 1, 8, 2)], 10), MALFORMED))
+    out.append(("src_len_2p32", RLEN, stream([("C", U32 - 16, 0, 16)], 16), MALFORMED))
+    out.append(("src_len_2p32_plus_16", RLEN, stream([("C", U32 - 16, 0, 32)], 32), MALFORMED))
+    out.append(("dst_len_2p32_plus_16", RLEN, stream([("C", H, U32 - 16, 32)], 16), MALFORMED))
+    out.append(("add_dst_len_wraps", RLEN, stream([("A", U32 - 8, rng.randbytes(24))], 16), MALFORMED))
+    assert all(sm.Stream.of(c[2]).version_size <= 65536 for c in out)
+    return out
+
+
+def update_cases():
+    """In-place streams, hand-made: the buffer holds R (buf_cap covers it), the
+    version is its first bytes.  Later COPYs read what earlier commands stored
+    (memmove order), one range stays as R left it, one COPY overlaps itself."""
+    rng = random.Random(0x2337)
+    out = []
+    for ref_len in LOW + [RLEN]:
+        placed, at = [], 0
+        for s, n in _window_copies(ref_len):
+            placed.append(("C", s, at, n))
+            at += n + 3                                          # three bytes of R (zeros) stay between them
+        placed += [("C", ref_len - 9, at, 9), ("C", 5, at + 9, 40), ("C", at + 20, at + 25, 20), ("C", at + 25, at + 21, 20),
+                   ("A", at + 60, rng.randbytes(11)), ("C", H - 33, 2, 3), ("C", 0, at + 71, 12)]
+        out.append((f"windows_ref_{ref_len:#x}", ref_len, stream(placed, at + 90, flags=1), OK))
+    placed, at = [], 0
+    for k in range(1000):   # more than three 4 KiB windows: COPYs from around and above 2^31 to increasing dst, then ADDs
+        n = rng.randint(1, 24)
+        placed.append(("C", rng.choice([H - 33, H + 100001, RLEN - 64]) + rng.randrange(0, 40), at, n))
+        at += n + rng.randint(0, 5)
+    placed += [("A", rng.randrange(0, at - 9), rng.randbytes(rng.randint(1, 9))) for _ in range(40)]
+    out.append(("three_windows", RLEN, stream(placed, at, flags=1), OK))
+    assert len(out[-1][2]) > 3 * 4096
+    # bsz = max(ref_len, version_size) bounds both dst + len and a COPY's src + len
+    for e in LOW:
+        out.append((f"src_len_past_bsz_{e:#x}", e, stream([("C", H - 33, 0, 8), ("C", e - 1, 8, 2)], 10, flags=1), MALFORMED))
+        out.append((f"dst_len_past_bsz_{e:#x}", e, stream([("C", 0, e - 1, 2)], 10, flags=1), MALFORMED))
+    out.append(("src_len_2p32", RLEN, stream([("C", U32 - 16, 0, 16)], 16, flags=1), MALFORMED))
+    out.append(("src_len_2p32_plus_16", RLEN, stream([("C", U32 - 16, 0, 32)], 32, flags=1), MALFORMED))
+    out.append(("dst_len_2p32_plus_16", RLEN, stream([("C", 0, U32 - 16, 32)], 16, flags=1), MALFORMED))
+    out.append(("add_dst_len_wraps", RLEN, stream([("A", U32 - 8, rng.randbytes(24))], 16, flags=1), MALFORMED))
+    out.append(("standard_flag", RLEN, stream([("C", H - 33, 0, 8)], 8), UNSUPPORTED))
+    assert all(sm.Stream.of(c[2]).version_size <= 65536 for c in out)
+    return out
+
+
+# ── the corpus, built once ──
+
+_cache = {}
+
+
+def corpus():
+    if not _cache:
+        _cache.update(compose=compose_cases(), invert=invert_cases(), read=read_cases(), splice=splice_cases(),
+                      decode=decode_cases(), update=update_cases())
+    return _cache
+
+
+def _fields(d, into, rebase=0):
+    st = sm.Stream.of(d)
+    into["version_size"].add(st.version_size)
+    for kind, ref, dst, n in st.cmds:
+        into["dst"].add(dst)
+        into["dst+len"].add(dst + n)
+        if kind == 1:
+            into["src"].add(ref + rebase)
+            into["src+len"].add(ref + rebase + n)
+
+
+def reach():
+    """Per operator and quantity, the values the accepted cases take."""
+    c = corpus()
+    out = {op: {q: set() for q in QUANTITIES} for op in c}
+    for _, a, b, st in c["compose"]:
+        if st == OK:
+            _fields(a, out["compose"])
+            _fields(b, out["compose"])
+    for op in ("invert", "read", "decode", "update"):
+        for case in c[op]:
+            if case[3] == OK:
+                _fields(case[2], out[op])
+                out[op]["ref_len"].add(case[1])
+    for _, whole, segs, deltas, _, st in c["splice"]:
+        if st == OK:   # of the spliced delta: sources rebased, dst in the whole V
+            into = out["splice"]
+            into["ref_len"].add(whole[1])
+            into["version_size"].add(whole[3])
+            for (sro, _, svo, _), d in zip(segs, deltas):
+                for kind, ref, dst, n in sm.Stream.of(d).cmds:
+                    into["dst"].add(svo - whole[2] + dst)
+                    into["dst+len"].add(svo - whole[2] + dst + n)
+                    if kind == 1:
+                        into["src"].add(ref + sro - whole[0])
+                        into["src+len"].add(ref + sro - whole[0] + n)
+    return out

@@ -1,0 +1,298 @@
+"""GPU: the kernels that consume command streams, at offsets and sizes in the
+upper half of the u32 range, against the sparse model (tests/sparse_model.py)
+on the corpus of tests/high_offset_cases.py: exact bytes, exact statuses.
+
+The kernels keep src, dst and len in 32-bit registers and widen by hand where
+two of them meet; the other GPU tests never feed them an offset above a few
+MiB.  Here one reference of 2^32 - 1 - 2^20 bytes sits on the device once per
+module (zeros plus the corpus's windows) and every stream names a prefix of it.
+The harnesses are the siblings' (arenas at odd offsets, guard bytes, the sizing
+run): ComposePlan and SplicePlan take theirs as they are; InvertPlan's and
+ReadPlan's are subclassed only to take their reference from the shared arena
+instead of building one from bytes.  DecodePlan and UpdatePlan are driven
+directly: the update harness downloads its whole buffer after a run, which here
+is the 4 GiB arena.  Decode and update run without CRC checks (one block would
+checksum 4 GiB); the decode_large test runs with them, on a version of
+2^31 + 2^20 + 3 bytes whose expected CRC comes from the model's combine.
+
+Device memory: 4 GiB for R, and about 4.2 GiB more while the decode_large test
+compares its output (2 GiB of output plus the compare's temporary).
+"""
+from __future__ import annotations
+
+import ctypes as C
+import struct
+
+import numpy as np
+import pytest
+
+import high_offset_cases as hc
+import sparse_model as sm
+from test_gpu_compose import Run as ComposeRun
+from test_gpu_index_chunked import ChunkedRun
+from test_gpu_invert import Run as InvertBase
+from test_gpu_splice import Run as SpliceRun
+
+pytestmark = pytest.mark.gpu
+
+OK, TOO_LARGE, CAPACITY, DST_CRC = 0, 3, 7, 10
+GUARD = 0xA5
+HEAD = 1 << 17   # what an update of this corpus may change of the arena: its versions are below 64 KiB
+
+
+@pytest.fixture(scope="module")
+def arena(torch_cuda):
+    """R on the device: zeros and the corpus's windows."""
+    torch = torch_cuda
+    t = torch.zeros(hc.RLEN, dtype=torch.uint8, device="cuda")
+    for o, b in hc.R.windows():
+        t[o:o + len(b)] = torch.frombuffer(bytearray(b), dtype=torch.uint8).cuda()
+    torch.cuda.synchronize()
+    assert t.data_ptr() % 16 == 0
+    yield t
+    del t
+    torch.cuda.empty_cache()
+
+
+def _packed(r, expected):
+    """A run of a transform plan: every status and size, the outputs packed without gaps, the guards intact."""
+    at = 0
+    for k, (name, (st, exp)) in enumerate(expected):
+        assert r.status[k] == st, (name, r.status[k], st)
+        assert r.offs[k] == at, name
+        assert r.result(k) == exp, name
+        at += len(exp)
+    assert r.offs[-1] == at
+    assert r.bytes[at:] == bytes([GUARD]) * (r.out_cap - at)
+
+
+# 1. compose: one batch of every pair
+def test_compose_plan(dg, ctx, torch_cuda):
+    cases = hc.corpus()["compose"]
+    pairs = [(a, b) for _, a, b, _ in cases]
+    expected = [(name, sm.compose(a, b)) for name, a, b, _ in cases]
+    assert [e[1][0] for e in expected] == [c[3] for c in cases]
+    r = ComposeRun(torch_cuda, dg, ctx, pairs).run()
+    assert r.sizing_st == [st or CAPACITY for st in r.status] and r.sizing_off == r.offs
+    _packed(r, expected)
+
+
+# 2. invert: one batch, every stream against a prefix of the shared reference
+class InvertRun(InvertBase):
+    def __init__(self, torch, dg, ctx, d_ref, items):
+        """items: (ref_len, A).  The streams at odd offsets between guard bytes, the last one at the arena's end."""
+        self.torch, self.dg, self.ctx, self.n = torch, dg, ctx, len(items)
+        self.offsets = False
+        buf, descs = bytearray([GUARD]) * 3, []
+        for k, (ref_len, a) in enumerate(items):
+            descs.append((0, ref_len, len(buf), len(a)))
+            buf += a + (b"" if k + 1 == self.n else bytes([GUARD]) * 7)
+        self.plan = dg.InvertPlan(ctx, descs)
+        self.off = torch.zeros(self.n + 1, dtype=torch.int64, device="cuda")
+        self.st = torch.full((self.n,), -1, dtype=torch.int32, device="cuda")
+        self.arena = [d_ref, torch.frombuffer(buf, dtype=torch.uint8).cuda()]
+
+
+def test_invert_plan(dg, ctx, torch_cuda, arena):
+    cases = hc.corpus()["invert"]
+    expected = [(name, sm.invert(hc.R.head(ref_len), a)) for name, ref_len, a, _ in cases]
+    assert [e[1][0] for e in expected] == [c[3] for c in cases]
+    r = InvertRun(torch_cuda, dg, ctx, arena, [(ref_len, a) for _, ref_len, a, _ in cases])
+    assert r.plan.output_bound > sum(c[1] for c in cases)   # (the bound counts every R whole: the run gets what the model needs)
+    r.run(out_cap=sum(len(e[1][1]) for e in expected) + 100)
+    _packed(r, expected)
+
+
+# 3. splice: one batch of every group whose geometry a plan accepts; the others are refused at create
+def test_splice_plan(dg, ctx, torch_cuda):
+    cases = hc.corpus()["splice"]
+    refused = [c for c in cases if sm.splice_geometry(c[1], c[2])]
+    assert [c[5] for c in refused] == [TOO_LARGE] * 2
+    for name, whole, segs, deltas, _, st in refused:
+        with pytest.raises(dg.DeltaError) as e:
+            dg.SplicePlan(ctx, [whole], [0, len(segs)], segments=segs, caps=[len(d) for d in deltas])
+        assert e.value.code == st, name
+    cases = [c for c in cases if c not in refused]
+    expected = [(name, sm.splice(whole, segs, deltas, crc)) for name, whole, segs, deltas, crc, _ in cases]
+    assert [e[1][0] for e in expected] == [c[5] for c in cases]
+    r = SpliceRun(torch_cuda, dg, ctx, [(segs, deltas, whole, crc) for _, whole, segs, deltas, crc, _ in cases]).run()
+    assert r.sizing_st == [st or CAPACITY for st in r.status] and r.sizing_off == r.offs
+    _packed(r, expected)
+    # the spliced header's dst_crc is the model's combine of the segments' arbitrary header values
+    one = next(k for k, c in enumerate(cases) if c[0] == "one_copy_65")
+    assert r.result(one)[17:25] == expected[one][1][1][17:25] != bytes(8)
+
+
+# 4. read: the one-block index, then the chunked index over it, the same requests after each
+class ReadRun(ChunkedRun):
+    def __init__(self, torch, dg, ctx, d_ref, items, requests, sizes):
+        """items: (ref_len, delta), every reference a prefix of d_ref; the streams as test_gpu_read.Run lays them out."""
+        self.torch, self.dg, self.ctx, self.items = torch, dg, ctx, items
+        self.n = len(items)
+        dlt, self.streams = bytearray(), []
+        for k, (ref_len, d) in enumerate(items):
+            dlt += bytes([GUARD]) * ((1 + (3 * k) % 15) if k % 2 else (-len(dlt) % 16))
+            self.streams.append((0, ref_len, len(dlt), len(d)))
+            dlt += d
+        self.d_ref = d_ref
+        self.d_delta = torch.frombuffer(dlt + b"\0", dtype=torch.uint8).cuda()
+        self.plan = dg.ReadPlan(ctx, self.streams, len(requests))
+        self.d_sst = torch.full((self.n,), -1, dtype=torch.int32, device="cuda")
+        self.set_requests(requests, sizes)
+
+    def check_model(self, cases):
+        """Run.check with the sparse model: every length and status, and the output arena compared whole."""
+        exp = self.before.copy()
+        for j, (s, off, ln) in enumerate(self.requests):
+            name, ref_len, d, _, _ = cases[s]
+            st, got = sm.read(hc.R.head(ref_len), d, off, ln)
+            assert self.st[j] == st, (name, off, ln, self.st[j], st)
+            assert self.out_len[j] == len(got), (name, off, ln, self.out_len[j], len(got))
+            o, room = self.slots[j]
+            assert len(got) <= room
+            exp[o:o + len(got)] = np.frombuffer(got, dtype=np.uint8)
+        bad = np.flatnonzero(self.after != exp)
+        if bad.size:
+            at = int(bad[0])
+            j = max(k for k, (o, _) in enumerate(self.slots) if o - 64 <= at)
+            raise AssertionError(f"{bad.size} bytes differ, the first at {at}: {cases[self.requests[j][0]][0]} "
+                                 f"{self.requests[j]}, slot at {self.slots[j]}, got {int(self.after[at])} want {int(exp[at])}")
+
+
+@pytest.mark.parametrize("chunk_bytes", [4096, 65536])
+def test_read_plan(dg, ctx, torch_cuda, arena, chunk_bytes):
+    cases = hc.corpus()["read"]
+    reqs = [(s, off, ln) for s, c in enumerate(cases) for off, ln in c[4]]
+    sizes = [0 if cases[s][3] else sm.Stream.of(cases[s][2]).version_size for s, _, _ in reqs]
+    r = ReadRun(torch_cuda, dg, ctx, arena, [(c[1], c[2]) for c in cases], reqs, sizes)
+    serial, st_serial = r.index().indexes()
+    assert st_serial == [c[3] for c in cases]
+    r.run().check_model(cases)
+    r.set_requests(reqs, sizes)   # a fresh output arena
+    r.d_sst.fill_(-1)
+    r.plan.chunk_index(chunk_bytes)
+    chunked, st_chunked = r.index_chunked().indexes()
+    assert st_chunked == st_serial
+    for c, a, b in zip(cases, serial, chunked):
+        assert a[:32] == b[:32], c[0]
+        assert c[3] or (a == b and len(a) == 32 + 8 * (len(c[2]) // 1024 + 1)), c[0]
+    r.run().check_model(cases)
+    assert r.stream_st == st_serial
+
+
+# 5. decode: standard streams whose COPYs read R's windows above 2^31
+def test_decode_plan(dg, ctx, torch_cuda, arena):
+    torch = torch_cuda
+    cases = hc.corpus()["decode"]
+    pad, descs, dlt, at = 48, [], bytearray([GUARD]) * 5, 16
+    for name, ref_len, d, st in cases:
+        vs = sm.Stream.of(d).version_size
+        descs.append((0, ref_len, len(dlt), len(d), at, vs))
+        dlt += d + bytes([GUARD]) * 3
+        at += vs + pad + (-vs % 16) + 1   # odd output offsets
+    plan = dg.DecodePlan(ctx, descs, ignore_hash=True)
+    d_delta = torch.frombuffer(dlt, dtype=torch.uint8).cuda()
+    out = torch.full((at,), GUARD, dtype=torch.uint8, device="cuda")
+    lens = torch.full((len(cases),), -1, dtype=torch.int64, device="cuda")
+    sts = torch.full((len(cases),), -1, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    plan.run(arena.data_ptr(), d_delta.data_ptr(), out.data_ptr(), lens.data_ptr(), sts.data_ptr(), ctx.stream)
+    torch.cuda.synchronize()
+    got, lens, sts = bytes(out.cpu().numpy()), lens.cpu().tolist(), sts.cpu().tolist()
+    exp = bytearray([GUARD]) * at
+    for k, (name, ref_len, d, st) in enumerate(cases):
+        assert sts[k] == st == sm.decode_status(ref_len, d, descs[k][5]), (name, sts[k], st)
+        if st == OK:
+            vs = descs[k][5]
+            assert lens[k] == vs, name
+            exp[descs[k][4]:descs[k][4] + vs] = sm.replay(hc.R.head(ref_len), d, (0, vs))
+            assert got[descs[k][4]:descs[k][4] + vs] == exp[descs[k][4]:descs[k][4] + vs], name
+    ok = [k for k, c in enumerate(cases) if c[3] == OK]
+    last = descs[ok[-1]][4] + descs[ok[-1]][5]
+    assert got[:last + pad] == bytes(exp[:last + pad]), "a byte outside an output, or in a refused stream's"
+
+
+# 6. update: hand-made in-place streams in the arena itself, one plan each; the arena's head is put back after each
+def test_update_plan(dg, ctx, torch_cuda, arena):
+    torch = torch_cuda
+    cases = hc.corpus()["update"]
+    head = arena[:HEAD].clone()
+    before = bytes(head.cpu().numpy())
+    tail = arena[hc.RLEN - 4096:].clone()
+    mid = arena[hc.H - 4096:hc.H + 4096].clone()
+    try:
+        for name, ref_len, d, st in cases:
+            plan = dg.UpdatePlan(ctx, [(0, hc.RLEN, ref_len, 0, len(d))], ignore_hash=True)
+            d_delta = torch.frombuffer(bytearray(d), dtype=torch.uint8).cuda()
+            olen = torch.full((1,), -1, dtype=torch.int64, device="cuda")
+            sts = torch.full((1,), -1, dtype=torch.int32, device="cuda")
+            torch.cuda.synchronize()
+            plan.run(arena.data_ptr(), d_delta.data_ptr(), olen.data_ptr(), sts.data_ptr(), stream=ctx.stream)
+            torch.cuda.synchronize()
+            got = bytes(arena[:HEAD].cpu().numpy())
+            arena[:HEAD].copy_(head)
+            assert sts.item() == st == sm.update_status(ref_len, d, hc.RLEN), (name, sts.item(), st)
+            if st == OK:
+                vs = sm.Stream.of(d).version_size
+                assert olen.item() == vs, name
+                assert got[:vs] == sm.replay(hc.R.head(ref_len), d, (0, vs)), name
+                assert got[vs:] == before[vs:], name   # (ref_len is far above: nothing of [version_size, ref_len) is touched here)
+            else:
+                assert olen.item() == 0 and got == before, name
+            plan.close()
+        assert torch.equal(arena[hc.RLEN - 4096:], tail) and torch.equal(arena[hc.H - 4096:hc.H + 4096], mid)
+    finally:
+        arena[:HEAD].copy_(head)
+        torch.cuda.synchronize()
+
+
+# 7. decode_large: a version that crosses 2^31, CRC checks on
+def test_decode_large_output_crosses_2p31(dg, ctx, orc, torch_cuda):
+    import random
+    torch = torch_cuda
+    rng = random.Random(0x2338)
+    MB = 1 << 20
+    B, T = rng.randbytes(MB), rng.randbytes(3)
+    R = B + T
+    n = 2049
+    vs = n * MB + 3
+    assert vs == hc.H + MB + 3
+    crc_b, crc_t = (int.from_bytes(orc.crc64_xz(x), "big") for x in (B, T))
+    dst_crc = sm.crc64_combine(sm.crc64_repeat(crc_b, MB, n), crc_t, 3)   # never from the device
+    body = b"".join(b"\x01" + struct.pack(">III", 0, k * MB, MB) for k in range(n)) + b"\x01" + struct.pack(">III", MB, n * MB, 3)
+    d = b"DLT\x03\x00" + struct.pack(">I", vs) + orc.crc64_xz(R) + dst_crc.to_bytes(8, "big") + body + b"\x00"
+    assert sm.decode_status(len(R), d) == OK and sm.replay(R, d, (vs - 5, vs)) == B[-2:] + T
+
+    def call(delta):
+        out = dg._lib.Buffer()
+        rc_ = dg.lib.dg_decode_large(ctx.handle, dg._lib._u8(R), len(R), dg._lib._u8(delta), len(delta), 0, 0, 0, C.byref(out))
+        return rc_, out
+
+    rc_, out = call(d)
+    try:
+        assert rc_ == OK and out.len == vs
+        host = np.ctypeslib.as_array(C.cast(out.data, C.POINTER(C.c_uint8)), shape=(vs,))
+        dev = torch.from_numpy(host).cuda()
+        want = torch.frombuffer(bytearray(B), dtype=torch.uint8).cuda()
+        assert bool((dev[:n * MB].view(n, MB) == want).all()), "a tile of the output is not B"
+        assert bytes(dev[n * MB:].cpu().numpy()) == T
+        del dev, host
+    finally:
+        dg.lib.dg_buffer_free(C.byref(out))
+    torch.cuda.empty_cache()
+    rc_, out = call(d[:20] + bytes([d[20] ^ 1]) + d[21:])   # one byte of the header's dst_crc
+    dg.lib.dg_buffer_free(C.byref(out))
+    assert rc_ == DST_CRC
+
+
+# 8. what the read plan refuses: a length of 4 GiB at create, a stream above 2^32 - 16 bytes for the chunked index
+def test_read_plan_limits(dg, ctx):
+    for s in [(0, 1 << 32, 0, 100), (0, 100, 0, 1 << 32)]:
+        with pytest.raises(dg.DeltaError) as e:
+            dg.ReadPlan(ctx, [s], 1)
+        assert e.value.code == TOO_LARGE
+    p = dg.ReadPlan(ctx, [(0, (1 << 32) - 1, 0, 0xFFFFFFF1)], 1)   # accepted: its index is delta_len / 128 + 64 bytes
+    with pytest.raises(dg.DeltaError) as e:
+        p.chunk_index(4096)
+    assert e.value.code == TOO_LARGE
+    p.close()
