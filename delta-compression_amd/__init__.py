@@ -30,6 +30,9 @@ Names and argument meanings follow the reference's interface for this path:
   apply.c:229-249, sliced).  ``ReadPlan.chunk_index`` / ``index_chunked`` index
   one large delta with the whole GPU (the same index), and ``decode_large(R,
   delta)`` is ``decode`` as that index plus ``tile_requests`` tiles of V.
+* ``read_lineage(R, deltas, off, length)`` / ``LineagePlan`` /
+  ``read_lineage_batch`` — the same read of a version that is several deltas
+  away from R (a delta on a delta on ... R), without rebuilding any version.
 * ``sketch`` / ``SketchPlan`` / ``sketch_batch`` / ``match_sketches`` /
   ``pick_bases`` — which buffer to encode against: min-wise resemblance
   sketches over the encoders' fingerprints and base selection by the exact
@@ -115,6 +118,12 @@ from ._lib import (  # noqa: F401
     encode_large,
     read_range,
     read_ranges,
+    LineagePlan,
+    read_lineage,
+    read_lineage_batch,
+    lineage_work_items,
+    LINEAGE_BASE,
+    LINEAGE_MAX_DEPTH,
     tile_requests,
     decode_large,
     sketch,
@@ -135,6 +144,7 @@ __all__ = [
     "InvertDesc", "InvertPlan", "invert", "invert_batch",
     "SplicePlan", "segment_pairs", "splice", "splice_batch", "sketch_windows", "encode_large",
     "ReadPlan", "ReadReq", "ReadStream", "read_range", "read_ranges", "tile_requests", "decode_large",
+    "LineagePlan", "read_lineage", "read_lineage_batch", "lineage_work_items", "LINEAGE_BASE", "LINEAGE_MAX_DEPTH",
     "SketchPlan", "sketch", "sketch_batch", "match_sketches", "match_sketches_device", "pick_bases", "SKETCH_BINS", "SKETCH_EMPTY",
     "MATCH_NONE", "MATCH_ALL", "MATCH_NOT_SELF", "MATCH_EARLIER",
     "crc64_xz", "decode", "default_context", "encode", "encode_batch", "encode_pipelined", "info", "lib",

@@ -274,6 +274,16 @@ def _load() -> C.CDLL:
         "dg_read_plan_index_stage_times": (C.c_int, [vp, C.POINTER(C.c_float), C.POINTER(C.c_char_p), C.c_int]),
         "dg_tile_requests": (C.c_int, [u32, u32, C.POINTER(ReadReq), u32, C.POINTER(u32)]),
         "dg_decode_large": (C.c_int, [vp, u8p, sz, u8p, sz, C.c_int, u32, u32, C.POINTER(Buffer)]),
+        "dg_read_lineage": (C.c_int, [u8p, sz, C.POINTER(u8p), C.POINTER(sz), u32, u64, u64, C.POINTER(Buffer)]),
+        "dg_lineage_work_items": (u32, []),
+        "dg_lineage_plan_create": (C.c_int, [vp, C.POINTER(u32), u32, C.POINTER(vp)]),
+        "dg_lineage_plan_run": (C.c_int, [vp, vp, vp, vp, u32, vp, vp, vp, vp]),
+        "dg_lineage_plan_set_timing": (C.c_int, [vp, C.c_int]),
+        "dg_lineage_plan_stage_times": (C.c_int, [vp, C.POINTER(C.c_float), C.POINTER(C.c_char_p), C.c_int]),
+        "dg_lineage_plan_destroy": (None, [vp]),
+        "dg_read_lineage_batch": (C.c_int, [vp, C.POINTER(u8p), C.POINTER(sz), C.POINTER(u8p), C.POINTER(sz),
+                                            C.POINTER(u32), u32, C.POINTER(ReadReq), u32, C.POINTER(Buffer),
+                                            C.POINTER(i32)]),
         "dg_sketch": (C.c_int, [u8p, sz, u32, u32, C.POINTER(u64)]),
         "dg_sketch_match": (C.c_int, [C.POINTER(u64), u32, C.POINTER(u64), u32, u32, C.c_int, u32, u32,
                                       C.POINTER(Match)]),
@@ -1188,6 +1198,95 @@ def read_ranges(items: Sequence[Tuple[bytes, bytes]], requests: Sequence[Tuple[i
     outs = (Buffer * m)()
     st = (C.c_int32 * m)()
     ctx.check(lib.dg_read_batch(ctx.handle, rp, rl, dp, dl, n, rq, m, outs, st), "dg_read_batch")
+    res = []
+    for j in range(m):
+        res.append(C.string_at(outs[j].data, outs[j].len) if outs[j].len else b"")
+        lib.dg_buffer_free(C.byref(outs[j]))
+    if status:
+        return res, list(st)
+    for j in range(m):
+        if st[j]:
+            raise DeltaError(st[j], f"request {j}")
+    return res
+
+
+LINEAGE_BASE = 0xFFFFFFFF   # DG_LINEAGE_BASE
+LINEAGE_MAX_DEPTH = 64      # DG_LINEAGE_MAX_DEPTH
+
+
+def lineage_work_items() -> int:
+    """Work items of a lineage request's stack on the device (dg_lineage_work_items)."""
+    return int(lib.dg_lineage_work_items())
+
+
+class LineagePlan(_Plan):
+    """dg_lineage_plan_t: byte ranges of versions that are several standard
+    deltas away from a whole buffer, read on the device without rebuilding any
+    version.  reads: the ReadPlan whose streams these are and whose index
+    passes index them (it must outlive this plan); parents[i]: LINEAGE_BASE or
+    the stream that makes stream i's reference.  run() serves a device array of
+    ReadReq, one block per request, as ReadPlan.run does."""
+
+    _prefix = "dg_lineage_plan"
+
+    def __init__(self, reads: "ReadPlan", parents: Sequence[int], max_requests: int):
+        self.ctx = reads.ctx
+        self.reads = reads
+        n = len(parents)
+        arr = (C.c_uint32 * max(n, 1))(*[int(p) for p in parents])
+        h = C.c_void_p()
+        self.ctx.check(lib.dg_lineage_plan_create(reads.handle, arr, int(max_requests), C.byref(h)),
+                       "dg_lineage_plan_create")
+        self._own(h)
+        self.max_requests = int(max_requests)
+
+    def run(self, d_ref: int, d_delta: int, d_reqs: int, n_req: int, d_out: int, d_out_len: int, d_status: int,
+            stream: int = 0):
+        self.ctx.check(lib.dg_lineage_plan_run(self.handle, d_ref or None, d_delta or None, d_reqs or None, int(n_req),
+                                               d_out or None, d_out_len or None, d_status or None, stream or None),
+                       "dg_lineage_plan_run")
+
+
+def read_lineage(R: bytes, deltas: Sequence[bytes], off: int, length: int) -> bytes:
+    """Bytes [off, off + length) of the version that deltas[0] on R, deltas[1]
+    on that version, ... make, clipped to it (dg_read_lineage): host only, no
+    CRC check, no version rebuilt."""
+    keep = [bytes(d) for d in deltas]
+    k = len(keep)
+    dp = (C.POINTER(C.c_uint8) * max(k, 1))(*[_u8(d) for d in keep])
+    dl = (C.c_size_t * max(k, 1))(*[len(d) for d in keep])
+    out = Buffer()
+    rc = lib.dg_read_lineage(_u8(R), len(R), dp, dl, k, int(off), int(length), C.byref(out))
+    if rc:
+        raise DeltaError(rc, "dg_read_lineage")
+    res = C.string_at(out.data, out.len) if out.len else b""
+    lib.dg_buffer_free(C.byref(out))
+    return res
+
+
+def read_lineage_batch(items: Sequence[Tuple[Optional[bytes], bytes]], parents: Sequence[int],
+                       requests: Sequence[Tuple[int, int, int]], ctx: Optional[Context] = None, status: bool = False):
+    """requests (stream, off, length) read on the device in one batch
+    (dg_read_lineage_batch) from items (R or None, delta): stream i's delta
+    applies to R where parents[i] is LINEAGE_BASE, else to the version of
+    stream parents[i] (its R is ignored).  Equal to read_lineage request by
+    request.  Raises DeltaError for the first failing request; with
+    status=True returns (results, statuses) instead, a failed request's result
+    being b""."""
+    ctx = ctx or default_context()
+    n, m = len(items), len(requests)
+    if m == 0:
+        return ([], []) if status else []
+    keep = [(bytes(r or b""), bytes(d)) for r, d in items]
+    rp = (C.POINTER(C.c_uint8) * max(n, 1))(*[_u8(r) for r, _ in keep])
+    dp = (C.POINTER(C.c_uint8) * max(n, 1))(*[_u8(d) for _, d in keep])
+    rl = (C.c_size_t * max(n, 1))(*[len(r) for r, _ in keep])
+    dl = (C.c_size_t * max(n, 1))(*[len(d) for _, d in keep])
+    par = (C.c_uint32 * max(n, 1))(*[int(p) for p in parents])
+    rq = (ReadReq * m)(*[ReadReq(int(s), int(o), int(ln), 0, 0) for s, o, ln in requests])
+    outs = (Buffer * m)()
+    st = (C.c_int32 * m)()
+    ctx.check(lib.dg_read_lineage_batch(ctx.handle, rp, rl, dp, dl, par, n, rq, m, outs, st), "dg_read_lineage_batch")
     res = []
     for j in range(m):
         res.append(C.string_at(outs[j].data, outs[j].len) if outs[j].len else b"")

@@ -14,6 +14,7 @@
  *   delta invert <ref> <delta_in> <delta_out> [--ignore-hash]
  *   delta pick [--seed-len P] [--bins K] <version> <candidate>...
  *   delta read <ref> <delta> <offset> <length> <output>
+ *   delta lineage <ref> <offset> <length> <output> <delta>...
  *
  * --inplace / inplace run the CRWI conversion on the host (dg_make_inplace,
  * main.c:279-283 and :427-480).  --splay applies to greedy only (its tie-break
@@ -106,6 +107,7 @@ static void usage(void)
 	    "  delta invert <ref> <delta_in> <delta_out> [--ignore-hash]\n"
 	    "  delta pick [--seed-len P] [--bins K] <version> <candidate>...\n"
 	    "  delta read <ref> <delta> <offset> <length> <output>\n"
+	    "  delta lineage <ref> <offset> <length> <output> <delta>...\n"
 	    "\n"
 	    "Algorithms: greedy, onepass, correcting (MI355X)\n"
 	    "\n"
@@ -539,6 +541,43 @@ static int cmd_read(int argc, char **argv)
 	return 0;
 }
 
+/* delta lineage <ref> <offset> <length> <output> <delta>...: bytes [offset,
+ * offset + length) of the version the deltas make of <ref>, the first on <ref>,
+ * each next one on the version before it; by the host function (no GPU, no
+ * CRC check, no version rebuilt) */
+static int cmd_lineage(int argc, char **argv)
+{
+	if (argc < 7) usage();
+	char *e1 = NULL, *e2 = NULL;
+	errno = 0;
+	unsigned long long off = strtoull(argv[3], &e1, 10), len = strtoull(argv[4], &e2, 10);
+	/* digits only: strtoull alone would take a sign or leading blanks */
+	if (errno || argv[3][0] < '0' || argv[3][0] > '9' || *e1 || argv[4][0] < '0' || argv[4][0] > '9' || *e2) {
+		fprintf(stderr, "delta_lineage: offset and length are decimal byte counts\n");
+		return 1;
+	}
+	const int k = argc - 6;
+	if (k > (int)DG_LINEAGE_MAX_DEPTH) {
+		fprintf(stderr, "delta_lineage: at most %u deltas\n", (unsigned)DG_LINEAGE_MAX_DEPTH);
+		return 1;
+	}
+	size_t rl, dl[DG_LINEAGE_MAX_DEPTH];
+	uint8_t *d[DG_LINEAGE_MAX_DEPTH];
+	uint8_t *r = read_file(argv[2], &rl);
+	for (int j = 0; j < k; j++) d[j] = read_file(argv[6 + j], &dl[j]);
+	dg_buffer_t o = {0};
+	int rc = dg_read_lineage(r, rl, (const uint8_t *const *)d, dl, (uint32_t)k, off, len, &o);
+	free(r);
+	for (int j = 0; j < k; j++) free(d[j]);
+	if (rc) {
+		fprintf(stderr, "delta_lineage: %s\n", dg_status_string(rc));
+		return 1;
+	}
+	write_file(argv[5], o.data, o.len);
+	dg_buffer_free(&o);
+	return 0;
+}
+
 /* delta pick [--seed-len P] [--bins K] <version> <candidate>...: which candidate
  * to encode the version against, by the host functions (no GPU) */
 static int cmd_pick(int argc, char **argv)
@@ -611,6 +650,7 @@ int main(int argc, char **argv)
 	if (strcmp(argv[1], "invert") == 0) return cmd_invert(argc, argv);
 	if (strcmp(argv[1], "pick") == 0) return cmd_pick(argc, argv);
 	if (strcmp(argv[1], "read") == 0) return cmd_read(argc, argv);
+	if (strcmp(argv[1], "lineage") == 0) return cmd_lineage(argc, argv);
 	usage();
 	return 1;
 }

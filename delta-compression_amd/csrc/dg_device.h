@@ -195,7 +195,7 @@ dg_context_t* plan_ctx(const dg_encode_plan_t* P);
 void plan_options(const dg_encode_plan_t* P, dg_algorithm_t* algo, dg_diff_options_t* opts);
 // the context's slots for code objects loaded at run time, one per module
 // (filled by load_kernels, dg_hostutil.h)
-enum : int { kCtxModInplace = 0, kCtxModUpdate = 1, kCtxModCompose = 2, kCtxModInvert = 3, kCtxModSketch = 4, kCtxModRead = 5, kCtxModSplice = 6, kCtxModIndex = 7, kCtxModules = 8 };
+enum : int { kCtxModInplace = 0, kCtxModUpdate = 1, kCtxModCompose = 2, kCtxModInvert = 3, kCtxModSketch = 4, kCtxModRead = 5, kCtxModSplice = 6, kCtxModIndex = 7, kCtxModLineage = 8, kCtxModules = 9 };
 void** ctx_module(dg_context_t* ctx, int slot, void (*release)(void*));
 const uint64_t* ctx_crc_tables(const dg_context_t* ctx);     // the CRC tables on the device (CrcArgs::tables)
 int ctx_fail(dg_context_t* ctx, int code, const char* msg);   // records dg_last_error, returns code

@@ -1295,6 +1295,128 @@ int dg_decode_large(dg_context_t *ctx, const uint8_t *r, size_t r_len,
                     const uint8_t *delta, size_t delta_len, int ignore_hash,
                     uint32_t chunk_bytes, uint32_t tile_bytes, dg_buffer_t *out);
 
+/* ── lineage reads: byte ranges through chains of deltas ─────────────────────
+ *
+ * A store keeps one buffer whole and every other version as a delta on a base
+ * that is usually itself a delta: backward deltas from the newest version
+ * (dg_invert), or trees whose parents dg_sketch_match chose.  A lineage is a base
+ * buffer R = V_0 and standard deltas d_1 .. d_k with V_j = apply(V_{j-1}, d_j).
+ * A lineage read returns bytes [off, off + n) of V_k, with pread's rule in 64
+ * bits: n = off >= |V_k| ? 0 : min(len, |V_k| - off).  That is exactly what k
+ * replays (apply.c:229-249) and a slice give; no V_j is built.  No CRC is
+ * checked, as for dg_read.
+ *
+ * Every delta of a lineage is sequential: its commands tile its version in
+ * stream order (each starts where the one before it ends, the last ends at
+ * version_size).  Every encoder, dg_compose, dg_invert and dg_splice emit such
+ * streams.  A caller with another valid stream directly on a base uses
+ * dg_read / dg_read_plan_run.
+ *
+ * Status of a read, the first that applies; the order is the same on the host
+ * and on the device:
+ *   1. DG_ERR_INVALID_ARG  (device) stream >= n_streams or reserved != 0;
+ *                          (host) k > DG_LINEAGE_MAX_DEPTH, a NULL argument;
+ *   2. walking from the requested delta towards its base, for each one:
+ *      a. its index status: what dg_read_plan_index reports for it, with the
+ *         size of the version below it as its ref_len (DG_ERR_MALFORMED,
+ *         DG_ERR_UNSUPPORTED for an in-place delta, or a passed-on status).  So
+ *         a COPY of d_j that leaves V_{j-1} is DG_ERR_MALFORMED;
+ *      b. DG_ERR_UNSUPPORTED if it is valid but not sequential;
+ *      c. (device) DG_ERR_INVALID_ARG if its ref_len is not its parent's
+ *         version_size.  A parent whose own index status is not 0 has no
+ *         version_size: that status, which is next in the order, is the result.
+ *   3. DG_OK.
+ *
+ * dg_read_lineage is pure host code: no context, no GPU.  deltas[0] is the
+ * delta on R, deltas[k - 1] the one whose version is read; k == 0 reads R
+ * itself.  Level j's ref_len is version_size of d_{j-1}'s header; a d_{j-1}
+ * without a readable header (shorter than 25 bytes, another magic) states none
+ * and d_j's COPYs are then checked against 2^32 - 1 (the walk ends at d_{j-1}
+ * with DG_ERR_MALFORMED unless d_j fails first).  DG_ERR_TOO_LARGE for an r_len
+ * or delta_len of 4 GiB or more.  Work memory is the n output bytes, one frame
+ * per level and 16 bytes per KiB of the deltas; time is a validating parse of
+ * every delta plus, per level, the commands that meet the range. */
+#define DG_LINEAGE_BASE 0xFFFFFFFFu
+#define DG_LINEAGE_MAX_DEPTH 64u
+int dg_read_lineage(const uint8_t *r, size_t r_len,
+                    const uint8_t *const *deltas, const size_t *delta_len, uint32_t k,
+                    uint64_t off, uint64_t len, dg_buffer_t *out);
+
+/* ── lineage reads of a batch on the device ──────────────────────────────────
+ *
+ * The lineages of a batch are a forest over the streams of a read plan:
+ * parent[i] is DG_LINEAGE_BASE or the index of another stream of the plan.
+ *   parent[i] == DG_LINEAGE_BASE: stream i's reference is ref_len bytes at
+ *      ref_off of the reference arena, as for dg_read_plan_run;
+ *   otherwise: ref_off is ignored and ref_len is what the caller states to be
+ *      the parent's version size; the index passes validate every COPY of the
+ *      stream against it (status c above holds the caller to it).
+ * At most DG_LINEAGE_MAX_DEPTH deltas lie between a stream and its base.
+ *
+ * dg_lineage_plan_create checks the forest on the host: a parent out of range,
+ * a cycle, or a depth above DG_LINEAGE_MAX_DEPTH is DG_ERR_INVALID_ARG, and
+ * dg_last_error says which stream.  The read plan must outlive the lineage
+ * plan, which uses its stream table and its index memory and owns only the
+ * parents; destroy the lineage plan first.  Streams are indexed by the read
+ * plan's own passes, dg_read_plan_index or dg_read_plan_index_chunked, with
+ * identical results; a run before either is DG_ERR_INVALID_ARG.
+ *
+ * Run.  One launch, one block per request; no allocation, no host
+ * synchronisation; n_req <= max_requests (DG_ERR_INVALID_ARG otherwise).
+ * Requests, slots and outputs are dg_read_plan_run's: d_status[j] as above,
+ * d_out_len[j] = n and the slice in d_out[out_off .. out_off + n) on DG_OK;
+ * bytes [n, len) of the slot are not touched; on a failing status n = 0 and
+ * the slot is not touched; nothing outside the slots is written.  out_off may
+ * have any alignment; d_out must be 16-byte aligned.
+ *
+ * Work memory is fixed: a request's block keeps a stack of
+ * dg_lineage_work_items() work items in LDS, whatever the data (DESIGN.md,
+ * "Lineage reads on the device").  No block waits for another.
+ *
+ * Cost.  A request parses, per level, the 4 KiB windows of that level's stream
+ * that hold commands meeting the range, once per piece the level above cut the
+ * range into: about depth x (n + windows touched) work.  Materialising every
+ * level (k dg_decode_plan_runs) moves every version whole, and composing
+ * (k - 1 dg_compose_plan_runs, an index pass, dg_read_plan_run) pays once for
+ * any number of later reads.  Measured with 1 % edits per level and one read
+ * per lineage of a whole batch (README.md): a 4 KiB lineage read is the
+ * fastest route for 1 MiB versions at every depth up to 16 and for 64 KiB
+ * versions up to depth 2; a 64 KiB read only up to depth 2 at 1 MiB; beyond
+ * that, materialise.  The item count of a range grows with the square of the
+ * depth (every level cuts the range at its own edits).
+ *
+ * Containment.  As for dg_read_plan_run: whatever the arenas hold, a stale
+ * index included, a run reads only reference and delta bytes of the plan's
+ * streams and writes only inside the requests' slots.  Under a stale index the
+ * kernel re-checks that the commands it walks follow one another and cover the
+ * range, every COPY's src + len <= ref_len, and the depth; a violation ends
+ * the request with DG_ERR_MALFORMED (bytes inside its slot are then
+ * unspecified), so a request cannot fan out.
+ *
+ * The kernel lives in dg_lineage.hsaco beside libdeltagpu.so and is loaded at
+ * create; DG_ERR_HIP with the path in dg_last_error when it is missing.  Stage
+ * timing as for the read plan: "read" (the kernel), "total". */
+typedef struct dg_lineage_plan dg_lineage_plan_t;
+uint32_t dg_lineage_work_items(void);
+int dg_lineage_plan_create(dg_read_plan_t *reads, const uint32_t *parent /* host, n_streams */,
+                           uint32_t max_requests, dg_lineage_plan_t **out);
+int dg_lineage_plan_run(dg_lineage_plan_t *plan, const uint8_t *d_ref, const uint8_t *d_delta,
+                        const dg_read_req_t *d_reqs, uint32_t n_req, uint8_t *d_out,
+                        uint32_t *d_out_len, int32_t *d_status, void *stream);
+int dg_lineage_plan_set_timing(dg_lineage_plan_t *plan, int slots);
+int dg_lineage_plan_stage_times(dg_lineage_plan_t *plan, float *ms, const char **names, int n);
+void dg_lineage_plan_destroy(dg_lineage_plan_t *plan);
+
+/* Host buffers, as dg_read_batch: refs[i] and ref_len[i] are read only for
+ * streams whose parent is DG_LINEAGE_BASE; for the others ref_len comes from
+ * the parent's header (2^32 - 1 when it has no readable header, as for
+ * dg_read_lineage).  The forest is checked as at create. */
+int dg_read_lineage_batch(dg_context_t *ctx, const uint8_t *const *refs, const size_t *ref_len,
+                          const uint8_t *const *deltas, const size_t *delta_len,
+                          const uint32_t *parent, uint32_t n_streams,
+                          const dg_read_req_t *reqs /* host */, uint32_t n_req,
+                          dg_buffer_t *outs, int32_t *status);
+
 /* ── reference selection: resemblance sketches and base matching ─────────────
  *
  * Every entry point above starts from a pair: the caller knows which R a V is
