@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Regenerate tests/golden/golden.json from the REFERENCE itself.
+"""Regenerate tests/golden/golden.json (and golden_inplace.json,
+golden_table_size.json) from the REFERENCE itself.
 
 The reference's tests hold no golden delta bytes (encoder
 output is pinned only by cross-implementation byte identity), so the fixtures
@@ -132,6 +133,37 @@ def make_inplace(ref, orc):
     with open(path, "w") as f:
         json.dump(out, f, indent=0)
     print(f"wrote {len(out['cases'])} in-place cases to {path}")
+    make_table_size(ref, orc)
+
+
+def make_table_size(ref, orc):
+    """Table sizes on both sides of 2^23 and 2^25 (tests/table_size_cases.py):
+    the planted-collision onepass pairs at each q, the 128 MiB pair at its own
+    q, and the correcting rows whose |F| straddles 2^23.  Hashes only; the
+    tests regenerate the inputs."""
+    import table_size_cases as T
+    out = {"generator": "reference src/c via oracle/_ref (ref_encode_pair)", "cases": []}
+
+    def add(name, algo, R, V, q, max_table=O.MAX_TABLE, buf_cap=O.BUF_CAP):
+        d = ref.encode(algo, R, V, p=16, q=q, buf_cap=buf_cap, max_table=max_table)
+        out["cases"].append(dict(name=name, algo=algo, q=q, max_table=max_table,
+                                 delta_len=len(d), delta_sha256=sha(d)))
+
+    for q in T.QS:
+        for name, R, V in T.onepass_cases(q):
+            add(name, O.ONEPASS, R, V, q)
+    R, V = T.natural_pair(orc)
+    add("natural_128MiB", O.ONEPASS, R, V, 1)
+    for r_len, q, mt, _ in T.CORRECTING_ROWS:
+        R, V = T.correcting_boundary_pair(r_len)
+        add(T.correcting_name(r_len, q, mt), O.CORRECTING, R, V, q, mt)
+    r_len, q, mt = T.BUF_CAP_1_ROW
+    R, V = T.correcting_boundary_pair(r_len)
+    add(T.correcting_name(r_len, q, mt, 1), O.CORRECTING, R, V, q, mt, buf_cap=1)
+    path = os.path.join(HERE, "golden_table_size.json")
+    with open(path, "w") as f:
+        json.dump(out, f, indent=0)
+    print(f"wrote {len(out['cases'])} table-size cases to {path}")
 
 
 if __name__ == "__main__":

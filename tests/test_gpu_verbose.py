@@ -35,6 +35,12 @@ def _cases(orc):
     low = bytes(rng.choice(b"ab") for _ in range(20000))               # low entropy: collisions
     yield "correcting", low, low[::-1], []
     yield "correcting", rng.randbytes(3000), rng.randbytes(3000), []
+    # |F| = 8388617 >= 2^23: the counters come from the Barrett checkpoint test
+    # (global build, then the LDS build over a 4099-slot table)
+    import table_size_cases as T
+    big_r, big_v = T.correcting_boundary_pair(4194312)
+    yield "correcting", big_r, big_v, ["--table-size", "1"]
+    yield "correcting", big_r, big_v, ["--max-table", "4096"]
 
 
 @pytest.mark.skipif(not os.path.exists(REF), reason="reference CLI not built (oracle/_ref)")
