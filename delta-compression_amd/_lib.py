@@ -1178,18 +1178,16 @@ def read_range(R: bytes, delta: bytes, off: int, length: int) -> bytes:
     return res
 
 
-def read_ranges(items: Sequence[Tuple[bytes, bytes]], requests: Sequence[Tuple[int, int, int]],
-                ctx: Optional[Context] = None, status: bool = False):
-    """requests (stream, off, length) read from the (R, delta) items on the
-    device in one batch (dg_read_batch); equal to read_range request by
-    request.  Raises DeltaError for the first failing request; with
-    status=True returns (results, statuses) instead, a failed request's result
-    being b""."""
+def _read_batch(items, parents, requests, ctx, status):
+    """read_ranges (parents None: dg_read_batch; every R is bytes) and
+    read_lineage_batch (dg_read_lineage_batch; an R may be None): the items and
+    the requests to C arrays, the call, the results out of the library's
+    buffers; raises, or returns the statuses."""
     ctx = ctx or default_context()
     n, m = len(items), len(requests)
     if m == 0:
         return ([], []) if status else []
-    keep = [(bytes(r), bytes(d)) for r, d in items]
+    keep = [(bytes(r if parents is None else r or b""), bytes(d)) for r, d in items]
     rp = (C.POINTER(C.c_uint8) * max(n, 1))(*[_u8(r) for r, _ in keep])
     dp = (C.POINTER(C.c_uint8) * max(n, 1))(*[_u8(d) for _, d in keep])
     rl = (C.c_size_t * max(n, 1))(*[len(r) for r, _ in keep])
@@ -1197,7 +1195,13 @@ def read_ranges(items: Sequence[Tuple[bytes, bytes]], requests: Sequence[Tuple[i
     rq = (ReadReq * m)(*[ReadReq(int(s), int(o), int(ln), 0, 0) for s, o, ln in requests])
     outs = (Buffer * m)()
     st = (C.c_int32 * m)()
-    ctx.check(lib.dg_read_batch(ctx.handle, rp, rl, dp, dl, n, rq, m, outs, st), "dg_read_batch")
+    if parents is None:
+        rc, what = lib.dg_read_batch(ctx.handle, rp, rl, dp, dl, n, rq, m, outs, st), "dg_read_batch"
+    else:
+        par = (C.c_uint32 * max(n, 1))(*[int(p) for p in parents])
+        rc = lib.dg_read_lineage_batch(ctx.handle, rp, rl, dp, dl, par, n, rq, m, outs, st)
+        what = "dg_read_lineage_batch"
+    ctx.check(rc, what)
     res = []
     for j in range(m):
         res.append(C.string_at(outs[j].data, outs[j].len) if outs[j].len else b"")
@@ -1208,6 +1212,16 @@ def read_ranges(items: Sequence[Tuple[bytes, bytes]], requests: Sequence[Tuple[i
         if st[j]:
             raise DeltaError(st[j], f"request {j}")
     return res
+
+
+def read_ranges(items: Sequence[Tuple[bytes, bytes]], requests: Sequence[Tuple[int, int, int]],
+                ctx: Optional[Context] = None, status: bool = False):
+    """requests (stream, off, length) read from the (R, delta) items on the
+    device in one batch (dg_read_batch); equal to read_range request by
+    request.  Raises DeltaError for the first failing request; with
+    status=True returns (results, statuses) instead, a failed request's result
+    being b""."""
+    return _read_batch(items, None, requests, ctx, status)
 
 
 LINEAGE_BASE = 0xFFFFFFFF   # DG_LINEAGE_BASE
@@ -1273,30 +1287,7 @@ def read_lineage_batch(items: Sequence[Tuple[Optional[bytes], bytes]], parents: 
     request.  Raises DeltaError for the first failing request; with
     status=True returns (results, statuses) instead, a failed request's result
     being b""."""
-    ctx = ctx or default_context()
-    n, m = len(items), len(requests)
-    if m == 0:
-        return ([], []) if status else []
-    keep = [(bytes(r or b""), bytes(d)) for r, d in items]
-    rp = (C.POINTER(C.c_uint8) * max(n, 1))(*[_u8(r) for r, _ in keep])
-    dp = (C.POINTER(C.c_uint8) * max(n, 1))(*[_u8(d) for _, d in keep])
-    rl = (C.c_size_t * max(n, 1))(*[len(r) for r, _ in keep])
-    dl = (C.c_size_t * max(n, 1))(*[len(d) for _, d in keep])
-    par = (C.c_uint32 * max(n, 1))(*[int(p) for p in parents])
-    rq = (ReadReq * m)(*[ReadReq(int(s), int(o), int(ln), 0, 0) for s, o, ln in requests])
-    outs = (Buffer * m)()
-    st = (C.c_int32 * m)()
-    ctx.check(lib.dg_read_lineage_batch(ctx.handle, rp, rl, dp, dl, par, n, rq, m, outs, st), "dg_read_lineage_batch")
-    res = []
-    for j in range(m):
-        res.append(C.string_at(outs[j].data, outs[j].len) if outs[j].len else b"")
-        lib.dg_buffer_free(C.byref(outs[j]))
-    if status:
-        return res, list(st)
-    for j in range(m):
-        if st[j]:
-            raise DeltaError(st[j], f"request {j}")
-    return res
+    return _read_batch(items, parents, requests, ctx, status)
 
 
 class SketchPlan(_Plan):

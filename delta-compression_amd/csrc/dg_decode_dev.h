@@ -461,13 +461,19 @@ __device__ void dec_grouped_window(WP w, const uint16_t* cmds, uint32_t cnt, uin
 
 // ── the block's LDS and the window step ──
 //
-// A kernel declares the seven arrays
-//   uint8_t win[kDecWin + 32], uint16_t N1[kDecWin], NX[3 * kDecWin]      (16-byte aligned)
-//   uint16_t cmds[kDecMaxCmds], jumps[kDecMaxCmds / 16 + 2]
-//   uint32_t sh[8], bsum[2 * (kDecMaxCmds / 64 + 1)]
-// and dec_lds carves them.  NX holds N2, N4, N8 during the parse; afterwards
-// the waves' flat-copy scratch, then the grouped apply's arrays (or, outside
-// the window loop, the CRC tables: dec_crc_tables).
+// A kernel declares one `__shared__ DecLdsMem M;` and dec_lds carves it.  NX
+// holds N2, N4, N8 during the parse; afterwards the waves' flat-copy scratch,
+// then the grouped apply's arrays (or, outside the window loop, the CRC
+// tables: dec_crc_tables).
+struct DecLdsMem {
+	alignas(16) uint8_t win[kDecWin + 32];
+	alignas(16) uint16_t N1[kDecWin];
+	alignas(16) uint16_t NX[3 * kDecWin];
+	uint16_t cmds[kDecMaxCmds];
+	uint16_t jumps[kDecMaxCmds / 16 + 2];    // 16-command jumps, then the one 8-command jump
+	uint32_t sh[8];                          // walk results and window flags
+	uint32_t bsum[2 * (kDecMaxCmds / 64 + 1)];
+};
 struct DecLds {
 	ChainLds ch;       // win, N1, N2..N8 (NX), cmds, jumps, sh ([0..3], [6]: the walk's result)
 	uint16_t* NX;
@@ -476,18 +482,18 @@ struct DecLds {
 	DecScratch xs;     // this wave's
 	DecGroupLds grp;
 };
-__device__ __forceinline__ DecLds dec_lds(uint8_t* win, uint16_t* N1, uint16_t* NX, uint16_t* cmds, uint16_t* jumps,
-                                          uint32_t* sh, uint32_t* bsum) {
+__device__ __forceinline__ DecLds dec_lds(DecLdsMem& M) {
+	uint16_t* const NX = M.NX;
 	constexpr uint32_t kScratch = 64 * 4 + 128 * 4 + 64 * 8 + 64 * 8 + 64 * 4;
 	static_assert(kDecWaves * kScratch <= 3 * kDecWin * 2, "scratch fits NX");
 	static_assert(kDecWaves * kScratch + 4 * (4 * kDecMaxCmds + 4 + 8) + 2 * (2 * kDecMaxCmds + 2) + kDecMaxCmds <=
 	                  3 * kDecWin * 2,
 	              "grouped-apply arrays fit NX");
 	DecLds L;
-	L.ch = ChainLds{N1, NX, NX + kDecWin, NX + 2 * kDecWin, win, cmds, jumps, sh};
+	L.ch = ChainLds{M.N1, NX, NX + kDecWin, NX + 2 * kDecWin, M.win, M.cmds, M.jumps, M.sh};
 	L.NX = NX;
-	L.sh = sh;
-	L.bsum = bsum;
+	L.sh = M.sh;
+	L.bsum = M.bsum;
 	uint8_t* base = reinterpret_cast<uint8_t*>(NX) + (threadIdx.x >> 6) * kScratch;
 	L.xs.sp = reinterpret_cast<const uint8_t**>(base);
 	L.xs.dp = reinterpret_cast<uint8_t**>(base + 64 * 8);

@@ -1,9 +1,13 @@
 // dg_hostutil.h — what the host files that touch the device share (dg_host.cpp,
 // dg_host_io.cpp and the transform plans' dg_inplace_host.cpp,
 // dg_update_host.cpp, dg_compose_host.cpp, dg_invert_host.cpp, the sketch
-// plan's dg_sketch_host.cpp and the read plan's dg_read_host.cpp): device buffers, the stage-timing
-// event ring, the loader of the code objects that are loaded at run time, and
-// the small pieces of the plans and of the host-memory batch wrappers.
+// plan's dg_sketch_host.cpp, the read plan's dg_read_host.cpp and
+// dg_index_host.cpp and the lineage plan's dg_lineage_host.cpp): device
+// buffers, the stage-timing event ring, the loader of the code objects that
+// are loaded at run time, the timed launch of a run that is one kernel
+// (launch_timed: read, lineage), and the small pieces of the plans and of the
+// host-memory batch wrappers, among them the version_size a wrapper sizes a
+// stream's output from (header_vsize: in-place, read, lineage).
 // Internal; needs HIP.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -133,6 +137,20 @@ inline int hip_fail(dg_context_t* ctx, const char* what, hipError_t e) {
 	return ctx_fail(ctx, DG_ERR_HIP, msg.c_str());
 }
 
+// A run that is one kernel (read, lineage): the launch between the two events
+// of the run's set (ev, or nullptr: not timed).  `name` is the kernel's, for
+// the context's last error.
+inline int launch_timed(dg_context_t* ctx, hipEvent_t* ev, hipFunction_t fn, const char* name, uint32_t grid,
+                        uint32_t block, void* args, hipStream_t st) {
+	void* params[] = {args};
+	hipError_t e;
+	if (ev && (e = hipEventRecord(ev[0], st)) != hipSuccess) return hip_fail(ctx, "hipEventRecord", e);
+	if ((e = hipModuleLaunchKernel(fn, grid, 1, 1, block, 1, 1, 0, st, params, nullptr)) != hipSuccess)
+		return hip_fail(ctx, (std::string("launch of ") + name).c_str(), e);
+	if (ev && (e = hipEventRecord(ev[1], st)) != hipSuccess) return hip_fail(ctx, "hipEventRecord", e);
+	return DG_OK;
+}
+
 // what the transform plans' sizing reads of an encode plan (dg_plan.h)
 inline EncodePlanView encode_plan_view(const dg_encode_plan_t* enc) {
 	dg_algorithm_t algo;
@@ -160,6 +178,14 @@ struct ScopeExit {
 	ScopeExit(const ScopeExit&) = delete;
 	ScopeExit& operator=(const ScopeExit&) = delete;
 };
+
+// version_size as the delta's header states it (bytes 5..8, big-endian), or
+// `otherwise` where d does not begin with a header: what a wrapper sizes a
+// stream's output from before the device has judged the stream
+inline uint64_t header_vsize(const uint8_t* d, size_t dl, uint64_t otherwise = 0) {
+	if (dl < DG_HEADER_SIZE || memcmp(d, "DLT\x03", 4) != 0) return otherwise;
+	return ((uint64_t)d[5] << 24) | ((uint64_t)d[6] << 16) | ((uint64_t)d[7] << 8) | d[8];
+}
 
 // out takes a malloc'ed copy of len bytes at src (one byte allocated when len == 0); false: out of memory
 inline bool buffer_copy(dg_buffer_t* out, const uint8_t* src, uint64_t len) {

@@ -20,7 +20,8 @@
 //      chunk 0 is 25, the entry of chunk k + 1 is exit[entry of k]; a chunk the
 //      chain jumps over (inside a long payload) inherits the entry.  One
 //      dependent load per chunk.
-//   dg_index_fill_kernel     one block per chunk: from the chunk's true entry,
+//   dg_index_fill_kernel     one block per chunk: the walk dg_read_index_kernel
+//      runs (rd_index_walk, dg_read_walk_dev.h), from the chunk's true entry:
 //      the real window step (dec_window, dg_decode_dev.h, bounds checks
 //      included) until a command at or after the chunk's end has been seen;
 //      the block writes exactly the index entries whose stride offsets lie in
@@ -39,6 +40,7 @@
 #include "dg_decode_dev.h"
 #include "dg_index_dev.h"
 #include "dg_read_dev.h"
+#include "dg_read_walk_dev.h"
 
 using namespace dg;
 using namespace dgrd;
@@ -46,10 +48,8 @@ using namespace dgix;
 
 namespace {
 
-static_assert(kRdBlock == kDecBlock && kIxWin == kDecWin, "the window step is written for decode's block");
-static_assert(sizeof(RdHead) == 32 && sizeof(RdEnt) == 8, "index layout");
+static_assert(kIxWin == kDecWin, "the map kernel's windows are the window step's");
 static_assert(kIxWin % kRdStride == 0, "strides do not straddle chunks");
-constexpr uint32_t kIxBatches = kDecMaxCmds / 64;
 // doubling rounds until a window's longest chain (a command is 9 bytes or more) has left it
 constexpr uint32_t kIxRounds = 9;
 static_assert((1u << kIxRounds) >= kIxWin / 9 + 1, "2^rounds commands cover a window");
@@ -235,16 +235,9 @@ extern "C" __global__ __launch_bounds__(kRdBlock) __attribute__((amdgpu_waves_pe
 	const uint64_t c0 = (uint64_t)k * a.chunk_bytes, cend = c0 + a.chunk_bytes;
 	const uint64_t dl = s.dl;
 	if (s.st || c0 >= dl) return;
-	const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = lane_id();
-	__shared__ __attribute__((aligned(16))) uint8_t win[kDecWin + 32];
-	__shared__ __attribute__((aligned(16))) uint16_t N1[kDecWin];
-	__shared__ __attribute__((aligned(16))) uint16_t NX[3 * kDecWin];
-	__shared__ uint16_t cmds[kDecMaxCmds];
-	__shared__ uint16_t jumps[kDecMaxCmds / 16 + 2];
-	__shared__ uint32_t sh[8];
-	__shared__ uint32_t bsum[2 * (kDecMaxCmds / 64 + 1)];
-	__shared__ uint32_t qcnt[kIxBatches], qfirst[kIxBatches], qend[kIxBatches], qbrk[kIxBatches];   // per batch, of the chunk's own commands
-	const DecLds L = dec_lds(win, N1, NX, cmds, jumps, sh, bsum);
+	__shared__ DecLdsMem M;
+	__shared__ RdTileLds T;
+	const DecLds L = dec_lds(M);
 
 	const uint8_t* D = a.delta + s.doff;
 	RdEnt* E = reinterpret_cast<RdEnt*>(a.index + a.index_off[i] + sizeof(RdHead));
@@ -255,80 +248,12 @@ extern "C" __global__ __launch_bounds__(kRdBlock) __attribute__((amdgpu_waves_pe
 	const uint32_t khi = cend >= dl ? n_ent - 1u : (uint32_t)(cend / kRdStride) - 1u;
 	const IxChunk ck = a.chunks[g];
 
-	bool failed = false, own_any = false, brk = false;
-	uint32_t first_dst = 0, run_end = 0;
-	bool any = false;       // a command has been seen
-	uint32_t prev_s = 0;    // the stream offset of the last one
-	if (ck.live) {
-		uint64_t pos = ck.entry;
-		bool done = false, past = false;
-		while (!done && !past && pos < dl) {
-			const DecWin w = dec_window(L, D, dl, pos, false, s.vsize, ref_len);
-			if (w.bad) {
-				failed = true;
-				break;
-			}
-			const uint8_t* wp = win + w.shf;
-			const uint32_t nb = (w.cnt + 63) / 64;
-			for (uint32_t b = wave; b < nb; b += kDecWaves) {
-				const DecCmd c = dec_cmd(wp, cmds, 64 * b, w.cnt, pos);
-				const uint32_t j = 64 * b + lane;
-				const uint32_t sp = c.mine ? (uint32_t)pos + cmds[j] : 0u;
-				const bool own = c.mine && sp < cend;   // it starts in this chunk (the window may run past it)
-				const uint32_t dst32 = (uint32_t)c.dst, end32 = (uint32_t)(c.dst + c.len);   // <= vsize: checked
-				const uint32_t prev_end = wave_shr1z(end32);
-				const bool bk = own && lane > 0 && dst32 != prev_end;
-				const uint64_t bm = __ballot(bk);
-				const uint32_t no = uni((uint32_t)__builtin_popcountll(__ballot(own)));   // a prefix of the batch
-				const uint32_t f = rdlane(dst32, 0), en = rdlane(end32, no ? no - 1 : 0);
-				if (lane == 0) {
-					qcnt[b] = no;
-					qfirst[b] = f;
-					qend[b] = en;
-					qbrk[b] = bm ? 1u : 0u;
-				}
-				// the entries of this chunk the command is the first at or after
-				uint32_t k0 = 1, k1 = 0;
-				if (c.mine) {
-					k0 = j > 0 ? ((uint32_t)pos + cmds[j - 1]) / kRdStride + 1u : (any ? prev_s / kRdStride + 1u : klo);
-					k1 = umin32(sp / kRdStride, khi);
-				}
-				const bool wide = c.mine && k1 >= k0 && k1 - k0 >= 4;
-				if (c.mine && !wide)
-					for (uint32_t q = k0; q <= k1; ++q) E[q] = RdEnt{sp, dst32};
-				for (uint64_t m = __ballot(wide); m; m &= m - 1) {
-					const uint32_t kk = ffs64(m);
-					const RdEnt ent{rdlane(sp, kk), rdlane(dst32, kk)};
-					const uint32_t e1 = rdlane(k1, kk);
-					for (uint32_t q = rdlane(k0, kk) + lane; q <= e1; q += 64) E[q] = ent;
-				}
-			}
-			__syncthreads();
-			for (uint32_t b = 0; b < nb; ++b) {
-				if (!qcnt[b]) break;
-				if (qbrk[b] || (own_any && qfirst[b] != run_end)) brk = true;
-				if (!own_any) first_dst = qfirst[b];
-				own_any = true;
-				run_end = qend[b];
-			}
-			if (w.cnt) {
-				prev_s = (uint32_t)pos + cmds[w.cnt - 1];
-				any = true;
-				past = prev_s >= cend;
-			}
-			done = w.done;
-			pos = w.next_pos;
-			__syncthreads();   // the window's LDS is the next window's
-		}
-	}
-	if (!failed) {   // the strides after the last command: nothing follows (END, the stream's end, or a chunk past them)
-		const uint32_t q0 = any ? prev_s / kRdStride + 1u : klo;
-		for (uint32_t q = q0 + tid; q <= khi; q += kRdBlock) E[q] = RdEnt{(uint32_t)dl, ~0u};
-	}
-	if (tid == 0) {
-		a.chunks[g].res = (failed ? kIxFailed : 0u) | (own_any ? kIxAny : 0u) | (brk ? kIxBrk : 0u);
-		a.chunks[g].first_dst = first_dst;
-		a.chunks[g].last_end = run_end;
+	// from the chunk's true entry (a chunk that is not live has no command: only its strides are filled)
+	const RdWalk r = rd_index_walk(L, T, D, dl, s.vsize, ref_len, E, ck.live ? ck.entry : dl, cend, klo, khi);
+	if (threadIdx.x == 0) {
+		a.chunks[g].res = (r.failed ? kIxFailed : 0u) | (r.t.any ? kIxAny : 0u) | (r.t.brk ? kIxBrk : 0u);
+		a.chunks[g].first_dst = r.t.first;
+		a.chunks[g].last_end = r.t.end;
 	}
 }
 

@@ -171,12 +171,8 @@ int dg_make_inplace_batch(dg_context_t* ctx, const uint8_t* const* r, const size
 		descs[i] = dg_inplace_desc_t{rt, r_len[i], dt, delta_len[i]};
 		rt += r_len[i];
 		dt += delta_len[i];
-		// an in-place delta is at most the stream plus its version bytes
-		// (header bytes 5..8) as ADD payload
-		uint64_t vs = 0;
-		if (delta_len[i] >= DG_HEADER_SIZE)
-			vs = ((uint64_t)delta[i][5] << 24) | ((uint64_t)delta[i][6] << 16) | ((uint64_t)delta[i][7] << 8) | delta[i][8];
-		out_cap += delta_len[i] + vs;
+		// an in-place delta is at most the stream plus its version bytes as ADD payload
+		out_cap += delta_len[i] + header_vsize(delta[i], delta_len[i]);
 	}
 	dg_inplace_plan_t* plan = nullptr;
 	int rc = dg_inplace_plan_create(ctx, descs.data(), n, policy, &plan);

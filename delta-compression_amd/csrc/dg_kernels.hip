@@ -474,17 +474,10 @@ __global__ __launch_bounds__(kDecBlock) __attribute__((amdgpu_waves_per_eu(4, 8)
 	const uint32_t i = blockIdx.x;
 	if (i >= a.n) return;
 	const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = lane_id();
-	__shared__ __attribute__((aligned(16))) uint8_t win[kDecWin + 32];
-	__shared__ __attribute__((aligned(16))) uint16_t N1[kDecWin];
-	// N2, N4, N8 during the parse; the waves' flat-copy scratch afterwards
-	__shared__ __attribute__((aligned(16))) uint16_t NX[3 * kDecWin];
-	__shared__ uint16_t cmds[kDecMaxCmds];
-	__shared__ uint16_t jumps[kDecMaxCmds / 16 + 2];   // 16-command jumps, then the one 8-command jump
-	__shared__ uint32_t sh[8];   // walk results and window flags
-	__shared__ uint32_t bsum[2 * (kDecMaxCmds / 64 + 1)];   // per batch: first written dst, max end
+	__shared__ DecLdsMem M;
 	__shared__ uint64_t cpart[2][kDecWaves];   // crc_check: per span, each wave's Horner partial
 	__shared__ uint32_t clast[2][kDecWaves];   // and its last segment
-	const DecLds L = dec_lds(win, N1, NX, cmds, jumps, sh, bsum);
+	const DecLds L = dec_lds(M);
 
 #ifdef DG_ONEPASS_PROF
 	uint64_t dprof[kDecProfN] = {};
@@ -526,7 +519,7 @@ __global__ __launch_bounds__(kDecBlock) __attribute__((amdgpu_waves_per_eu(4, 8)
 	uint32_t rlast = ~0u;
 	DPROF_T(tf0);
 	if (rcrc_early) {
-		const DecCrc ct = dec_crc_tables(NX, a);
+		const DecCrc ct = dec_crc_tables(M.NX, a);
 		__syncthreads();
 		const uint32_t nseg = crc_nseg((uintptr_t)R, rl, kDecCrcSeg);
 		const uintptr_t copy_hi = (uintptr_t)R + init / 16 * 16;
@@ -572,7 +565,7 @@ __global__ __launch_bounds__(kDecBlock) __attribute__((amdgpu_waves_per_eu(4, 8)
 		if (pos >= dl) break;   // missing END: end of input (as the reference's loop)
 		// ── 1-5. the window: load, command chain, bounds and order checks ──
 		const DecWin W = dec_window(L, D, dl, pos, inplace, bsz, inplace ? bsz : rl, DPROF_HOOK);
-		const uint8_t* w = win + W.shf;
+		const uint8_t* w = M.win + W.shf;
 		const uint32_t cnt = W.cnt, nb = (cnt + 63) / 64;
 		done = W.done;
 		if (W.bad) st = 8;
@@ -583,7 +576,7 @@ __global__ __launch_bounds__(kDecBlock) __attribute__((amdgpu_waves_per_eu(4, 8)
 				for (uint32_t b = wave; b < nb; b += kDecWaves) {
 					DPROF_INC(DP_BATCHES);
 					DPROF_T(tq0);
-					const DecCmd c = dec_cmd(w, cmds, 64 * b, cnt, pos);
+					const DecCmd c = dec_cmd(w, M.cmds, 64 * b, cnt, pos);
 #ifdef DG_ONEPASS_PROF
 					asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #endif
@@ -593,7 +586,7 @@ __global__ __launch_bounds__(kDecBlock) __attribute__((amdgpu_waves_per_eu(4, 8)
 					DPROF_ADD(DP_C_FLAT, tq1);
 				}
 			} else {
-				dec_grouped_window(w, cmds, cnt, pos, inplace, O, R, D, L.grp);
+				dec_grouped_window(w, M.cmds, cnt, pos, inplace, O, R, D, L.grp);
 			}
 		}
 		DPROF_T(tq2);
@@ -619,7 +612,7 @@ __global__ __launch_bounds__(kDecBlock) __attribute__((amdgpu_waves_per_eu(4, 8)
 		const uint64_t* KF = Lv + kCrcLevels * kCrcNibTabWords;   // x^(8 seg), x^(-8t), x^(8 seg k) k = 2..4
 		// LDS (the dead doubling arrays): the row tables and x^(8 * 64 KiB);
 		// 16 KiB segments read as rows of 64 x 8 bytes (coalesced)
-		const DecCrc ct = dec_crc_tables(NX, a);
+		const DecCrc ct = dec_crc_tables(M.NX, a);
 		const uint64_t* TK = ct.TK;
 		__syncthreads();
 		const uintptr_t sa[2] = {(uintptr_t)R, (uintptr_t)O};

@@ -48,6 +48,7 @@
 
 #include "dg_decode_dev.h"
 #include "dg_lineage_dev.h"
+#include "dg_read_walk_dev.h"
 
 using namespace dg;
 using namespace dgrd;
@@ -57,7 +58,6 @@ namespace {
 
 static_assert(kLnBlock == kDecBlock, "the window step is written for decode's block");
 static_assert(kLnItems >= kLnMaxDepth + 2, "the stack's progress argument");
-constexpr uint32_t kLnBatches = kDecMaxCmds / 64;
 
 // one stream of the request's path (level 0: the requested one)
 struct LnLevel {
@@ -67,44 +67,25 @@ struct LnLevel {
 	uint32_t dl, vsize, ref_len, n_ent;
 };
 
-// the command's intersection with V[lo, hi), its destination relative to lo
-__device__ __forceinline__ void ln_clip(DecCmd& c, uint64_t lo, uint64_t hi) {
-	if (!c.mine) return;
-	const uint64_t s = max(c.dst, lo), e = min(c.dst + c.len, hi);
-	if (e > s) {
-		c.src += s - c.dst;
-		c.len = e - s;
-		c.dst = s - lo;
-	} else {
-		c.len = 0;
-		c.dst = 0;
-	}
-}
-
 }  // namespace
 
 extern "C" __global__ __launch_bounds__(kLnBlock) void dg_lineage_read_kernel(LnArgs a) {
 	const uint32_t jq = blockIdx.x;
 	if (jq >= a.n_req) return;
 	const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = lane_id();
-	__shared__ __attribute__((aligned(16))) uint8_t win[kDecWin + 32];
-	__shared__ __attribute__((aligned(16))) uint16_t N1[kDecWin];
-	__shared__ __attribute__((aligned(16))) uint16_t NX[3 * kDecWin];
-	__shared__ uint16_t cmds[kDecMaxCmds];
-	__shared__ uint16_t jumps[kDecMaxCmds / 16 + 2];
-	__shared__ uint32_t sh[8];
-	__shared__ uint32_t bsum[2 * (kDecMaxCmds / 64 + 1)];
-	__shared__ uint32_t qfirst[kLnBatches], qend[kLnBatches], qbrk[kLnBatches], qkids[kLnBatches], qdir[kLnBatches];   // per batch
+	__shared__ DecLdsMem M;
+	__shared__ RdTileLds T;   // per batch: where it starts and ends in V, whether its commands follow one another
+	__shared__ uint32_t qkids[kRdBatches], qdir[kRdBatches];   // and an item's child COPYs and pieces in it
 	__shared__ LnLevel path[kLnMaxDepth];
 	__shared__ __attribute__((aligned(16))) uint4 stk[kLnItems];   // lo, hi, out_base, pos (0: enter through the index)
 	__shared__ uint8_t stk_lv[kLnItems];
 	__shared__ __attribute__((aligned(16))) uint4 stg[kLnItems];   // a run's children, in stream order
 	__shared__ __attribute__((aligned(16))) uint4 cst[kLnRun];     // and its continuations
-	const DecLds L = dec_lds(win, N1, NX, cmds, jumps, sh, bsum);
+	const DecLds L = dec_lds(M);
 	// the pieces a run copies as they are: (src, slot offset, len, kind), in NX behind the waves' flat-copy
 	// scratch (the grouped apply's arrays, which this kernel never uses); dead while a window is parsed
 	static_assert(kDecWaves * 2048 + 16 * kLnDirect <= 3 * kDecWin * 2, "the piece list fits NX");
-	uint4* dls = reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(NX) + kDecWaves * 2048);
+	uint4* dls = reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(M.NX) + kDecWaves * 2048);
 
 	// ── 1. the path and the status (every thread, uniform; thread 0 keeps the levels) ──
 	const RdReq rq = a.reqs[jq];
@@ -180,20 +161,8 @@ extern "C" __global__ __launch_bounds__(kLnBlock) void dg_lineage_read_kernel(Ln
 		const uint8_t* R = a.ref + (on_base ? uni64(pl->ref_off) : 0ull);
 		uint32_t pos = uni(top.w);
 		if (pos == 0) {
-			// the last entry whose dst is <= lo; the commands before its command end at or before its dst
-			const uint32_t lo = uni(top.x);
 			const RdEnt* E = reinterpret_cast<const RdEnt*>(a.index + uni64(pl->ent_off));
-			uint32_t x = 0, y = uni(pl->n_ent);
-			while (x < y) {
-				const uint32_t mid = (x + y) >> 1;
-				if (E[mid].dst <= lo) x = mid + 1;
-				else y = mid;
-			}
-			pos = 25;
-			if (x > 0) {
-				const uint32_t p = E[x - 1].spos;
-				if (p >= 25 && p < dl) pos = p;
-			}
+			pos = rd_entry_pos(E, uni(pl->n_ent), uni(top.x), dl);
 		}
 		if (pos >= dl) {
 			bad = true;   // the index accepted this stream and lo < hi <= its version_size: reached only with a stale index
@@ -204,33 +173,17 @@ extern "C" __global__ __launch_bounds__(kLnBlock) void dg_lineage_read_kernel(Ln
 			bad = true;   // (stale index)
 			break;
 		}
-		const uint8_t* wp = win + w.shf;
+		const uint8_t* wp = M.win + w.shf;
 		const uint32_t nb = (w.cnt + 63) / 64;
-		// per batch: where it starts and ends in V, whether its commands follow one another
 		for (uint32_t b = wave; b < nb; b += kDecWaves) {
-			const DecCmd c = dec_cmd(wp, cmds, 64 * b, w.cnt, (uint64_t)pos);
-			const uint32_t dst32 = (uint32_t)c.dst, end32 = (uint32_t)(c.dst + c.len);   // <= vs: checked
-			const uint32_t prev_end = wave_shr1z(end32);   // (every lane takes part)
-			const bool brk = c.mine && lane > 0 && dst32 != prev_end;
-			const uint64_t bm = __ballot(brk);
-			const uint32_t nm = uni(umin32(64u, w.cnt - 64 * b));
-			const uint32_t f = rdlane(dst32, 0), e = rdlane(end32, nm - 1);
-			if (lane == 0) {
-				qfirst[b] = f;
-				qend[b] = e;
-				qbrk[b] = bm ? 1u : 0u;
-			}
+			const DecCmd c = dec_cmd(wp, M.cmds, 64 * b, w.cnt, (uint64_t)pos);
+			rd_tile_batch(T, b, c, c.mine);
 		}
 		__syncthreads();
-		const uint32_t wfirst = qfirst[0];
-		uint32_t run = wfirst;
-		bool gap = false;
-		for (uint32_t b = 0; b < nb; ++b) {
-			if (qbrk[b] || qfirst[b] != run) gap = true;
-			run = qend[b];
-		}
-		const uint32_t wend = run;   // the window's commands tile [wfirst, wend)
-		if (gap) {
+		RdTiling wt;
+		rd_tile_fold(T, nb, wt);
+		const uint32_t wfirst = wt.first, wend = wt.end;   // the window's commands tile [wfirst, wend)
+		if (wt.brk) {
 			bad = true;   // (stale index)
 			break;
 		}
@@ -274,9 +227,9 @@ extern "C" __global__ __launch_bounds__(kLnBlock) void dg_lineage_read_kernel(Ln
 			// its child COPYs and the pieces copied as they are (ADDs; COPYs from R), per batch
 			for (uint32_t b = wave; b < nb; b += kDecWaves) {
 				uint64_t km = 0, dm = 0;
-				if (qend[b] > lo && qfirst[b] < hi) {
-					DecCmd c = dec_cmd(wp, cmds, 64 * b, w.cnt, (uint64_t)pos);
-					ln_clip(c, lo, hi);
+				if (T.end[b] > lo && T.first[b] < hi) {
+					DecCmd c = dec_cmd(wp, M.cmds, 64 * b, w.cnt, (uint64_t)pos);
+					rd_clip(c, lo, hi);
 					const bool kid = c.mine && !on_base && c.kind == 1 && c.len != 0;
 					km = __ballot(kid);
 					dm = __ballot(c.mine && c.len != 0 && !kid);
@@ -308,14 +261,14 @@ extern "C" __global__ __launch_bounds__(kLnBlock) void dg_lineage_read_kernel(Ln
 			const bool cut = push < kids;
 			// the clipped commands: pieces and child COPYs staged
 			for (uint32_t b = wave; b < nb; b += kDecWaves) {
-				if (!(qend[b] > lo && qfirst[b] < hi)) continue;
+				if (!(T.end[b] > lo && T.first[b] < hi)) continue;
 				uint32_t kb = 0, db = 0;
 				for (uint32_t q = 0; q < b; ++q) {
 					kb += qkids[q];
 					db += qdir[q];
 				}
-				DecCmd c = dec_cmd(wp, cmds, 64 * b, w.cnt, (uint64_t)pos);
-				ln_clip(c, lo, hi);
+				DecCmd c = dec_cmd(wp, M.cmds, 64 * b, w.cnt, (uint64_t)pos);
+				rd_clip(c, lo, hi);
 				const bool kid = c.mine && !on_base && c.kind == 1 && c.len != 0;
 				const bool direct = c.mine && c.len != 0 && !kid;
 				const uint64_t km = __ballot(kid), dm = __ballot(direct);
@@ -328,7 +281,7 @@ extern "C" __global__ __launch_bounds__(kLnBlock) void dg_lineage_read_kernel(Ln
 				if (kid && before < push) stg[nk + before] = make_uint4((uint32_t)c.src, (uint32_t)(c.src + c.len), ob + (uint32_t)c.dst, 0u);
 				if (kid && cut && before == push)
 					// the continuation restarts at this command: its dst is lo + c.dst (children before it: dst > lo)
-					cst[nc] = make_uint4(lo + (uint32_t)c.dst, hi, ob + (uint32_t)c.dst, pos + cmds[64 * b + lane]);
+					cst[nc] = make_uint4(lo + (uint32_t)c.dst, hi, ob + (uint32_t)c.dst, pos + M.cmds[64 * b + lane]);
 			}
 			if (!cut && cont && tid == 0) cst[nc] = make_uint4(wend, hi, ob + (wend - lo), (uint32_t)w.next_pos);
 			nk += push;

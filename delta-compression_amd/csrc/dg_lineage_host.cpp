@@ -43,11 +43,6 @@ struct dg_lineage_plan {
 
 namespace {
 
-uint64_t header_vsize(const uint8_t* d, size_t dl, uint64_t otherwise) {
-	if (dl < DG_HEADER_SIZE || memcmp(d, "DLT\x03", 4) != 0) return otherwise;
-	return ((uint64_t)d[5] << 24) | ((uint64_t)d[6] << 16) | ((uint64_t)d[7] << 8) | d[8];
-}
-
 // the forest: every parent in range, no cycle, at most DG_LINEAGE_MAX_DEPTH deltas down to a base
 int check_forest(dg_context_t* ctx, const uint32_t* parent, uint32_t n) {
 	char msg[160];
@@ -141,15 +136,11 @@ int dg_lineage_plan_run(dg_lineage_plan_t* P, const uint8_t* d_ref, const uint8_
 	if (!P) return DG_ERR_INVALID_ARG;
 	dg_context_t* ctx = P->ctx;
 	if (!read_plan_indexed(P->reads)) return ctx_fail(ctx, DG_ERR_INVALID_ARG, "lineage plan: no index pass of the read plan has run");
-	if (n_req > P->max_req) return ctx_fail(ctx, DG_ERR_INVALID_ARG, "lineage plan: more requests than max_requests");
-	if (n_req == 0) return DG_OK;
-	if (!d_reqs || !d_out || !d_out_len || !d_status || (P->n && (!d_ref || !d_delta)))
-		return ctx_fail(ctx, DG_ERR_INVALID_ARG, "null device buffer");
-	if ((uintptr_t)d_out & 15) return ctx_fail(ctx, DG_ERR_INVALID_ARG, "the output arena must be 16-byte aligned");
+	const int rc = read_run_check(ctx, "lineage plan", n_req, P->max_req, P->n != 0, d_ref, d_delta, d_reqs, d_out, d_out_len, d_status);
+	if (rc || n_req == 0) return rc;
 	if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return ctx_fail(ctx, DG_ERR_HIP, "hipSetDevice failed");
 	hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)dg_context_stream(ctx);
 	const ReadPlanView v = read_plan_view(P->reads);
-	hipEvent_t* ev = P->ring.next();
 	LnArgs a{};
 	a.ref = d_ref;
 	a.delta = d_delta;
@@ -163,13 +154,7 @@ int dg_lineage_plan_run(dg_lineage_plan_t* P, const uint8_t* d_ref, const uint8_
 	a.status = d_status;
 	a.n_streams = P->n;
 	a.n_req = n_req;
-	void* params[] = {&a};
-	hipError_t e;
-	if (ev && (e = hipEventRecord(ev[0], st)) != hipSuccess) return hip_fail(ctx, "hipEventRecord", e);
-	if ((e = hipModuleLaunchKernel(P->fn[0], n_req, 1, 1, kLnBlock, 1, 1, 0, st, params, nullptr)) != hipSuccess)
-		return hip_fail(ctx, "launch of dg_lineage_read_kernel", e);
-	if (ev && (e = hipEventRecord(ev[1], st)) != hipSuccess) return hip_fail(ctx, "hipEventRecord", e);
-	return DG_OK;
+	return launch_timed(ctx, P->ring.next(), P->fn[0], "dg_lineage_read_kernel", n_req, kLnBlock, &a, st);
 }
 
 void dg_lineage_plan_destroy(dg_lineage_plan_t* P) { plan_destroy(P); }
@@ -181,92 +166,23 @@ int dg_read_lineage_batch(dg_context_t* ctx, const uint8_t* const* refs, const s
 		return DG_ERR_INVALID_ARG;
 	for (uint32_t j = 0; j < n_req; ++j) outs[j] = dg_buffer_t{nullptr, 0};
 	if (n_req == 0) return DG_OK;
-	int rc = check_forest(ctx, parent, n_streams);
-	if (rc) return rc;
-	// the bases' references packed 16 bytes apart in one arena, the deltas packed
-	// in another, every request's slot 16 bytes apart in a third
-	std::vector<dg_read_stream_t> sv(n_streams);
-	uint64_t rt = 0, dt = 0, ot = 0;
-	for (uint32_t i = 0; i < n_streams; ++i) {
-		const bool on_base = parent[i] == DG_LINEAGE_BASE;
-		if ((on_base && ref_len[i] && !refs[i]) || (delta_len[i] && !deltas[i])) return DG_ERR_INVALID_ARG;
-		// a parent without a readable header states no size: its own status ends the request
-		const uint64_t rl = on_base ? ref_len[i] : header_vsize(deltas[parent[i]], delta_len[parent[i]], 0xFFFFFFFFull);
-		sv[i] = dg_read_stream_t{on_base ? rt : 0, rl, dt, delta_len[i]};
-		if (on_base) rt = (rt + rl + 15) & ~15ull;
-		dt += delta_len[i];
-	}
-	std::vector<dg_read_req_t> rv(reqs, reqs + n_req);
-	for (uint32_t j = 0; j < n_req; ++j) {
-		rv[j].out_off = ot;
-		// a slot no larger than the stream's version (its header says)
-		const uint64_t vs = rv[j].stream < n_streams ? header_vsize(deltas[rv[j].stream], delta_len[rv[j].stream], 0) : 0;
-		ot = (ot + std::min<uint64_t>(rv[j].len, vs) + 15) & ~15ull;
-	}
-	dg_read_plan_t* plan = nullptr;
-	rc = dg_read_plan_create(ctx, sv.data(), n_streams, n_req, &plan);
+	const int rc = check_forest(ctx, parent, n_streams);   // before anything is allocated
 	if (rc) return rc;
 	dg_lineage_plan_t* lin = nullptr;
-	ScopeExit guard([&] {
-		dg_lineage_plan_destroy(lin);
-		dg_read_plan_destroy(plan);
-	});
-	if ((rc = dg_lineage_plan_create(plan, parent, n_req, &lin)) != DG_OK) return rc;
-	hipStream_t st = (hipStream_t)dg_context_stream(ctx);
-	DevBuf d_ref, d_delta, d_req, d_out, d_len, d_st;
-	std::vector<uint8_t> h_ref, h_delta, h_out;
-	std::vector<uint32_t> lens(n_req);
-	std::vector<int32_t> stv(n_req);
-	try {
-		h_ref.resize(rt);
-		h_delta.resize(dt);
-	} catch (...) {
-		return DG_ERR_NOMEM;
-	}
-	for (uint32_t i = 0; i < n_streams; ++i) {
-		if (parent[i] == DG_LINEAGE_BASE && ref_len[i]) memcpy(h_ref.data() + sv[i].ref_off, refs[i], ref_len[i]);
-		if (delta_len[i]) memcpy(h_delta.data() + sv[i].delta_off, deltas[i], delta_len[i]);
-	}
-	if (d_ref.alloc_nonnull(rt) || d_delta.alloc_nonnull(dt) || d_req.alloc_nonnull(sizeof(RdReq) * n_req) ||
-	    d_out.alloc_nonnull(ot) || d_len.alloc_nonnull(4ull * n_req) || d_st.alloc_nonnull(4ull * n_req)) {
-		(void)hipGetLastError();
-		return ctx_fail(ctx, DG_ERR_NOMEM, "device allocation failed");
-	}
-	if ((rt && hipMemcpyAsync(d_ref.p, h_ref.data(), rt, hipMemcpyHostToDevice, st) != hipSuccess) ||
-	    (dt && hipMemcpyAsync(d_delta.p, h_delta.data(), dt, hipMemcpyHostToDevice, st) != hipSuccess) ||
-	    hipMemcpyAsync(d_req.p, rv.data(), sizeof(RdReq) * n_req, hipMemcpyHostToDevice, st) != hipSuccess)
-		return ctx_fail(ctx, DG_ERR_HIP, "upload failed");
-	if ((rc = dg_read_plan_index(plan, d_delta.as<uint8_t>(), nullptr, nullptr, nullptr, st)) != DG_OK) return rc;
-	rc = dg_lineage_plan_run(lin, d_ref.as<uint8_t>(), d_delta.as<uint8_t>(), d_req.as<dg_read_req_t>(), n_req,
-	                         d_out.as<uint8_t>(), d_len.as<uint32_t>(), d_st.as<int32_t>(), st);
-	if (rc) return rc;
-	if (hipMemcpyAsync(lens.data(), d_len.p, 4ull * n_req, hipMemcpyDeviceToHost, st) != hipSuccess ||
-	    hipMemcpyAsync(stv.data(), d_st.p, 4ull * n_req, hipMemcpyDeviceToHost, st) != hipSuccess ||
-	    hipStreamSynchronize(st) != hipSuccess)
-		return ctx_fail(ctx, DG_ERR_HIP, "download failed");
-	// the slots' used parts end at the last request that has bytes
-	uint64_t used = 0;
-	for (uint32_t j = 0; j < n_req; ++j)
-		if (!stv[j] && lens[j]) used = rv[j].out_off + lens[j];
-	try {
-		h_out.resize(used);
-	} catch (...) {
-		return DG_ERR_NOMEM;
-	}
-	if (used && (hipMemcpyAsync(h_out.data(), d_out.p, used, hipMemcpyDeviceToHost, st) != hipSuccess ||
-	             hipStreamSynchronize(st) != hipSuccess))
-		return ctx_fail(ctx, DG_ERR_HIP, "download failed");
-	BatchStatus bs{status};
-	for (uint32_t j = 0; j < n_req; ++j) {
-		const uint32_t nb = stv[j] ? 0u : lens[j];
-		const uint8_t none = 0;
-		if (!stv[j] && !buffer_copy(&outs[j], nb ? h_out.data() + rv[j].out_off : &none, nb)) {
-			for (uint32_t k = 0; k < j; ++k) dg_buffer_free(&outs[k]);
-			return DG_ERR_NOMEM;
-		}
-		bs.set(j, stv[j]);
-	}
-	return bs.result();
+	ReadBatchOps ops;
+	// a stream on the base reads refs[i]; any other the version of its parent's delta, whose header states its
+	// size (a parent without a readable header states none: its own status ends the request)
+	ops.ref_len = [&](uint32_t i, bool* in_arena) {
+		*in_arena = parent[i] == DG_LINEAGE_BASE;
+		return *in_arena ? (uint64_t)ref_len[i] : header_vsize(deltas[parent[i]], delta_len[parent[i]], 0xFFFFFFFFull);
+	};
+	ops.open = [&](dg_read_plan_t* plan) { return dg_lineage_plan_create(plan, parent, n_req, &lin); };
+	ops.close = [&] { dg_lineage_plan_destroy(lin); };
+	ops.run = [&](dg_read_plan_t*, const uint8_t* d_ref, const uint8_t* d_delta, const dg_read_req_t* d_reqs, uint32_t n,
+	              uint8_t* d_out, uint32_t* d_out_len, int32_t* d_status, void* stream) {
+		return dg_lineage_plan_run(lin, d_ref, d_delta, d_reqs, n, d_out, d_out_len, d_status, stream);
+	};
+	return read_batch(ctx, refs, deltas, delta_len, n_streams, reqs, n_req, outs, status, ops);
 }
 
 }  // extern "C"

@@ -1,6 +1,8 @@
 // dg_read_dev.h — what the range-read kernels (dg_read_dev.hip, built as the
 // stand-alone code object lib/dg_read.hsaco) and the host code that launches
-// them (dg_read_host.cpp) agree on.
+// them (dg_read_host.cpp) agree on; the chunked index pass (dg_index_dev.h)
+// and the lineage reads (dg_lineage_dev.h) leave and read the same index.
+// The device functions those three kernel files share are dg_read_walk_dev.h's.
 #pragma once
 #include <stdint.h>
 

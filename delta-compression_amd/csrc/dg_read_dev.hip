@@ -13,7 +13,9 @@
 //      the stream is sequential (every command starts where the one before it
 //      ends and the last ends at version_size: what every encoder, compose and
 //      invert emit) and, per kRdStride bytes of the stream, the first command
-//      at or after that offset with its dst (dg_read_dev.h).
+//      at or after that offset with its dst (dg_read_dev.h).  The loop is
+//      rd_index_walk (dg_read_walk_dev.h), which the chunked pass's fill
+//      kernel runs per chunk: here one chunk spans the stream.
 //   dg_read_kernel  one block per request: 256 threads and decode's 4 KiB
 //      window step, or (DG_READ_BLOCK=64, lib/dg_read_alt.hsaco, measurements
 //      only) one wave and 1 KiB windows.  A sequential stream is
@@ -33,54 +35,19 @@
 
 #include "dg_decode_dev.h"
 #include "dg_read_dev.h"
+#include "dg_read_walk_dev.h"
 
 using namespace dg;
 using namespace dgrd;
-
-namespace {
-
-static_assert(kRdBlock == kDecBlock, "the window step is written for decode's block");
-static_assert(sizeof(RdHead) == 32 && sizeof(RdEnt) == 8, "index layout");
-constexpr uint32_t kRdBatches = kDecMaxCmds / 64;
-
-// the command's intersection with V[lo, hi), its destination relative to lo
-__device__ __forceinline__ void rd_clip(DecCmd& c, uint64_t lo, uint64_t hi) {
-	if (!c.mine) return;
-	const uint64_t s = max(c.dst, lo), e = min(c.dst + c.len, hi);
-	if (e > s) {
-		c.src += s - c.dst;
-		c.len = e - s;
-		c.dst = s - lo;
-	} else {
-		c.len = 0;
-		c.dst = 0;
-	}
-}
-
-// dst of the command at window offset cx
-template <typename WP>
-__device__ __forceinline__ uint32_t rd_dst_at(WP w, uint32_t cx) {
-	uint32_t h[4];
-	win16(w + cx, h);
-	return (h[0] & 0xFFu) == 1u ? hdr_be32(h, 1) : hdr_be32(h, 0);
-}
-
-}  // namespace
 
 extern "C" __global__ __launch_bounds__(kRdBlock) __attribute__((amdgpu_waves_per_eu(4, 8))) void dg_read_index_kernel(
     RdIndexArgs a) {
 	const uint32_t i = blockIdx.x;
 	if (i >= a.n) return;
-	const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = lane_id();
-	__shared__ __attribute__((aligned(16))) uint8_t win[kDecWin + 32];
-	__shared__ __attribute__((aligned(16))) uint16_t N1[kDecWin];
-	__shared__ __attribute__((aligned(16))) uint16_t NX[3 * kDecWin];
-	__shared__ uint16_t cmds[kDecMaxCmds];
-	__shared__ uint16_t jumps[kDecMaxCmds / 16 + 2];
-	__shared__ uint32_t sh[8];
-	__shared__ uint32_t bsum[2 * (kDecMaxCmds / 64 + 1)];
-	__shared__ uint32_t qfirst[kRdBatches], qend[kRdBatches], qbrk[kRdBatches];   // per batch: first dst, last end, a break inside
-	const DecLds L = dec_lds(win, N1, NX, cmds, jumps, sh, bsum);
+	const uint32_t tid = threadIdx.x;
+	__shared__ DecLdsMem M;
+	__shared__ RdTileLds T;
+	const DecLds L = dec_lds(M);
 
 	const RdStream sd = a.streams[i];
 	uint64_t doff = sd.delta_off, dl = sd.delta_len;
@@ -99,72 +66,13 @@ extern "C" __global__ __launch_bounds__(kRdBlock) __attribute__((amdgpu_waves_pe
 	if (!st) vsize = be32(D + 5);
 	const uint32_t n_ent = st ? 0u : (uint32_t)(dl / kRdStride) + 1u;
 
-	bool seq = true, any = false;
-	uint32_t run_end = 0;   // where the last command seen ends
-	uint32_t prev_s = 0;    // its stream offset (any: there is one)
+	// the walk of one chunk that spans the stream (dg_read_walk_dev.h).  Sequential: its
+	// commands start at 0, each where the one before it ends, and the last ends at version_size
+	bool seq = false;
 	if (!st) {
-		uint64_t pos = 25;
-		bool done = false;
-		while (!done) {
-			if (pos >= dl) break;   // missing END: end of input (as the reference's loop)
-			const DecWin w = dec_window(L, D, dl, pos, false, vsize, sd.ref_len);
-			if (w.bad) {
-				st = 8;
-				break;
-			}
-			const uint8_t* wp = win + w.shf;
-			const uint32_t nb = (w.cnt + 63) / 64;
-			for (uint32_t b = wave; b < nb; b += kDecWaves) {
-				const DecCmd c = dec_cmd(wp, cmds, 64 * b, w.cnt, pos);
-				const uint32_t j = 64 * b + lane;
-				const uint32_t dst32 = (uint32_t)c.dst, end32 = (uint32_t)(c.dst + c.len);   // <= vsize: checked
-				const uint32_t prev_end = wave_shr1z(end32);   // (every lane takes part)
-				const bool brk = c.mine && lane > 0 && dst32 != prev_end;
-				const uint64_t bm = __ballot(brk);
-				const uint32_t nm = uni(umin32(64u, w.cnt - 64 * b));
-				const uint32_t f = rdlane(dst32, 0), e = rdlane(end32, nm - 1);
-				if (lane == 0) {
-					qfirst[b] = f;
-					qend[b] = e;
-					qbrk[b] = bm ? 1u : 0u;
-				}
-				// the entries this command is the first at or after: [k0, k1], the
-				// strides after the previous command's up to its own.  Up to four
-				// by its lane; more (after a long ADD payload) by the whole wave.
-				uint32_t s = 0, k0 = 1, k1 = 0;
-				if (c.mine) {
-					s = (uint32_t)pos + cmds[j];
-					k0 = j > 0 ? ((uint32_t)pos + cmds[j - 1]) / kRdStride + 1u : (any ? prev_s / kRdStride + 1u : 0u);
-					k1 = s / kRdStride;
-				}
-				const bool wide = c.mine && k1 >= k0 && k1 - k0 >= 4;
-				if (c.mine && !wide)
-					for (uint32_t k = k0; k <= k1; ++k) E[k] = RdEnt{s, dst32};
-				for (uint64_t m = __ballot(wide); m; m &= m - 1) {
-					const uint32_t kk = ffs64(m);
-					const RdEnt ent{rdlane(s, kk), rdlane(dst32, kk)};
-					const uint32_t e1 = rdlane(k1, kk);
-					for (uint32_t k = rdlane(k0, kk) + lane; k <= e1; k += 64) E[k] = ent;
-				}
-			}
-			__syncthreads();
-			for (uint32_t b = 0; b < nb; ++b) {
-				if (qbrk[b] || qfirst[b] != run_end) seq = false;
-				run_end = qend[b];
-			}
-			if (w.cnt) {
-				prev_s = (uint32_t)pos + cmds[w.cnt - 1];
-				any = true;
-			}
-			done = w.done;
-			pos = w.next_pos;
-			__syncthreads();   // the window's LDS is the next window's
-		}
-	}
-	if (!st) {
-		if (run_end != vsize) seq = false;
-		const uint32_t k0 = any ? prev_s / kRdStride + 1u : 0u;
-		for (uint32_t k = k0 + tid; k < n_ent; k += kRdBlock) E[k] = RdEnt{(uint32_t)dl, ~0u};
+		const RdWalk r = rd_index_walk(L, T, D, dl, vsize, sd.ref_len, E, 25, kRdNoEnd, 0, n_ent - 1u);
+		if (r.failed) st = 8;
+		seq = !r.t.brk && r.t.first == 0 && r.t.end == vsize;
 	}
 	if (tid == 0) {
 		RdHead h;
@@ -220,19 +128,9 @@ __device__ __forceinline__ void rd_request(const RdArgs& a) {
 
 	uint32_t pos = 25;
 	if (seq) {
-		// the last entry whose dst is <= off; the commands before its command end at or before its dst
 		const RdEnt* E = reinterpret_cast<const RdEnt*>(a.index + ix0 + sizeof(RdHead));
 		const uint64_t cap = (ix1 - ix0 - sizeof(RdHead)) / sizeof(RdEnt);
-		uint32_t x = 0, y = (uint32_t)min((uint64_t)h.n_ent, cap);
-		while (x < y) {
-			const uint32_t mid = (x + y) >> 1;
-			if (E[mid].dst <= lo) x = mid + 1;
-			else y = mid;
-		}
-		if (x > 0) {
-			const uint32_t p = E[x - 1].spos;
-			if (p >= 25 && p < dl) pos = p;
-		}
+		pos = rd_entry_pos(E, (uint32_t)min((uint64_t)h.n_ent, cap), lo, dl);
 	} else {
 		// zeros where no command writes (apply.c:233): byte edges, whole 16-byte words between
 		const uint32_t head = umin32(n, (16u - (uint32_t)((uintptr_t)O & 15u)) & 15u);
@@ -257,32 +155,26 @@ __device__ __forceinline__ void rd_request(const RdArgs& a) {
 
 	bool done = false;
 	if constexpr (T == 256) {
-		__shared__ __attribute__((aligned(16))) uint8_t win[kDecWin + 32];
-		__shared__ __attribute__((aligned(16))) uint16_t N1[kDecWin];
-		__shared__ __attribute__((aligned(16))) uint16_t NX[3 * kDecWin];
-		__shared__ uint16_t cmds[kDecMaxCmds];
-		__shared__ uint16_t jumps[kDecMaxCmds / 16 + 2];
-		__shared__ uint32_t sh[8];
-		__shared__ uint32_t bsum[2 * (kDecMaxCmds / 64 + 1)];
-		const DecLds L = dec_lds(win, N1, NX, cmds, jumps, sh, bsum);
+		__shared__ DecLdsMem M;
+		const DecLds L = dec_lds(M);
 		while (!done) {
 			if (pos >= dl) break;
 			const DecWin w = dec_window(L, D, dl, pos, false, h.vsize, rl);
 			if (w.bad) break;   // (the index accepted these bytes: reached only with a stale index)
-			const uint8_t* wp = win + w.shf;
+			const uint8_t* wp = M.win + w.shf;
 			const uint32_t nb = (w.cnt + 63) / 64;
 			// a sequential stream has nothing for the range after a command that starts at or after its end
-			if (seq && w.cnt && rd_dst_at(wp, cmds[w.cnt - 1]) >= hi) done = true;
+			if (seq && w.cnt && rd_dst_at(wp, M.cmds[w.cnt - 1]) >= hi) done = true;
 			if (w.free_win) {
 				for (uint32_t b = wave; b < nb; b += kDecWaves) {
-					DecCmd c = dec_cmd(wp, cmds, 64 * b, w.cnt, pos);
+					DecCmd c = dec_cmd(wp, M.cmds, 64 * b, w.cnt, pos);
 					rd_clip(c, lo, hi);
 					dec_flat_batch(c, false, O, R, D, L.xs);
 				}
 			} else if (wave == 0) {
 				// writes that overlap or go backwards: the clipped commands one by one in stream order
 				for (uint32_t b = 0; b < nb; ++b) {
-					DecCmd c = dec_cmd(wp, cmds, 64 * b, w.cnt, pos);
+					DecCmd c = dec_cmd(wp, M.cmds, 64 * b, w.cnt, pos);
 					rd_clip(c, lo, hi);
 					in_order(c);
 				}

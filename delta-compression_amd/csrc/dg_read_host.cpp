@@ -161,14 +161,10 @@ int dg_read_plan_run(dg_read_plan_t* P, const uint8_t* d_ref, const uint8_t* d_d
 	if (!P) return DG_ERR_INVALID_ARG;
 	dg_context_t* ctx = P->ctx;
 	if (!P->indexed) return ctx_fail(ctx, DG_ERR_INVALID_ARG, "read plan: dg_read_plan_index has not run");
-	if (n_req > P->max_req) return ctx_fail(ctx, DG_ERR_INVALID_ARG, "read plan: more requests than max_requests");
-	if (n_req == 0) return DG_OK;
-	if (!d_reqs || !d_out || !d_out_len || !d_status || (P->n && (!d_ref || !d_delta)))
-		return ctx_fail(ctx, DG_ERR_INVALID_ARG, "null device buffer");
-	if ((uintptr_t)d_out & 15) return ctx_fail(ctx, DG_ERR_INVALID_ARG, "the output arena must be 16-byte aligned");
+	const int rc = read_run_check(ctx, "read plan", n_req, P->max_req, P->n != 0, d_ref, d_delta, d_reqs, d_out, d_out_len, d_status);
+	if (rc || n_req == 0) return rc;
 	if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return ctx_fail(ctx, DG_ERR_HIP, "hipSetDevice failed");
 	hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)dg_context_stream(ctx);
-	hipEvent_t* ev = P->ring.next();
 	RdArgs a{};
 	a.ref = d_ref;
 	a.delta = d_delta;
@@ -181,13 +177,7 @@ int dg_read_plan_run(dg_read_plan_t* P, const uint8_t* d_ref, const uint8_t* d_d
 	a.status = d_status;
 	a.n_streams = P->n;
 	a.n_req = n_req;
-	void* params[] = {&a};
-	hipError_t e;
-	if (ev && (e = hipEventRecord(ev[0], st)) != hipSuccess) return hip_fail(ctx, "hipEventRecord", e);
-	if ((e = hipModuleLaunchKernel(P->fn[1], n_req, 1, 1, P->block, 1, 1, 0, st, params, nullptr)) != hipSuccess)
-		return hip_fail(ctx, "launch of dg_read_kernel", e);
-	if (ev && (e = hipEventRecord(ev[1], st)) != hipSuccess) return hip_fail(ctx, "hipEventRecord", e);
-	return DG_OK;
+	return launch_timed(ctx, P->ring.next(), P->fn[1], "dg_read_kernel", n_req, P->block, &a, st);
 }
 
 void dg_read_plan_destroy(dg_read_plan_t* P) { plan_destroy(P); }
@@ -199,14 +189,42 @@ int dg_read_batch(dg_context_t* ctx, const uint8_t* const* refs, const size_t* r
 		return DG_ERR_INVALID_ARG;
 	for (uint32_t j = 0; j < n_req; ++j) outs[j] = dg_buffer_t{nullptr, 0};
 	if (n_req == 0) return DG_OK;
-	// the references packed 16 bytes apart in one arena, the deltas packed in
-	// another, every request's slot 16 bytes apart in a third
+	ReadBatchOps ops;
+	ops.ref_len = [&](uint32_t i, bool* in_arena) {
+		*in_arena = true;
+		return (uint64_t)ref_len[i];
+	};
+	ops.run = dg_read_plan_run;
+	return read_batch(ctx, refs, deltas, delta_len, n_streams, reqs, n_req, outs, status, ops);
+}
+
+}  // extern "C"
+
+int dg::read_run_check(dg_context_t* ctx, const char* label, uint32_t n_req, uint32_t max_req, bool has_streams,
+                       const void* d_ref, const void* d_delta, const void* d_reqs, const void* d_out,
+                       const void* d_out_len, const void* d_status) {
+	if (n_req > max_req)
+		return ctx_fail(ctx, DG_ERR_INVALID_ARG, (std::string(label) + ": more requests than max_requests").c_str());
+	if (n_req == 0) return DG_OK;
+	if (!d_reqs || !d_out || !d_out_len || !d_status || (has_streams && (!d_ref || !d_delta)))
+		return ctx_fail(ctx, DG_ERR_INVALID_ARG, "null device buffer");
+	if ((uintptr_t)d_out & 15) return ctx_fail(ctx, DG_ERR_INVALID_ARG, "the output arena must be 16-byte aligned");
+	return DG_OK;
+}
+
+int dg::read_batch(dg_context_t* ctx, const uint8_t* const* refs, const uint8_t* const* deltas, const size_t* delta_len,
+                   uint32_t n_streams, const dg_read_req_t* reqs, uint32_t n_req, dg_buffer_t* outs, int32_t* status,
+                   const ReadBatchOps& ops) {
 	std::vector<dg_read_stream_t> sv(n_streams);
+	std::vector<uint64_t> packed(n_streams);   // bytes of refs[i] in the arena
 	uint64_t rt = 0, dt = 0, ot = 0;
 	for (uint32_t i = 0; i < n_streams; ++i) {
-		if ((ref_len[i] && !refs[i]) || (delta_len[i] && !deltas[i])) return DG_ERR_INVALID_ARG;
-		sv[i] = dg_read_stream_t{rt, ref_len[i], dt, delta_len[i]};
-		rt = (rt + ref_len[i] + 15) & ~15ull;
+		bool in_arena = false;
+		const uint64_t rl = ops.ref_len(i, &in_arena);
+		packed[i] = in_arena ? rl : 0;
+		if ((packed[i] && !refs[i]) || (delta_len[i] && !deltas[i])) return DG_ERR_INVALID_ARG;
+		sv[i] = dg_read_stream_t{in_arena ? rt : 0, rl, dt, delta_len[i]};
+		rt = (rt + packed[i] + 15) & ~15ull;
 		dt += delta_len[i];
 	}
 	std::vector<dg_read_req_t> rv(reqs, reqs + n_req);
@@ -214,17 +232,18 @@ int dg_read_batch(dg_context_t* ctx, const uint8_t* const* refs, const size_t* r
 		rv[j].out_off = ot;
 		// a slot no larger than the stream's version (its header says; the kernel
 		// stores min(len, version_size - off) bytes at the most)
-		uint64_t vs = 0;
-		if (rv[j].stream < n_streams && delta_len[rv[j].stream] >= DG_HEADER_SIZE) {
-			const uint8_t* d = deltas[rv[j].stream];
-			vs = ((uint64_t)d[5] << 24) | ((uint64_t)d[6] << 16) | ((uint64_t)d[7] << 8) | d[8];
-		}
+		const uint32_t s = rv[j].stream;
+		const uint64_t vs = s < n_streams ? header_vsize(deltas[s], delta_len[s]) : 0;
 		ot = (ot + std::min<uint64_t>(rv[j].len, vs) + 15) & ~15ull;
 	}
 	dg_read_plan_t* plan = nullptr;
 	int rc = dg_read_plan_create(ctx, sv.data(), n_streams, n_req, &plan);
 	if (rc) return rc;
-	ScopeExit guard([&] { dg_read_plan_destroy(plan); });
+	ScopeExit guard([&] {
+		if (ops.close) ops.close();
+		dg_read_plan_destroy(plan);
+	});
+	if (ops.open && (rc = ops.open(plan)) != DG_OK) return rc;
 	hipStream_t st = (hipStream_t)dg_context_stream(ctx);
 	DevBuf d_ref, d_delta, d_req, d_out, d_len, d_st;
 	std::vector<uint8_t> h_ref, h_delta, h_out;
@@ -237,7 +256,7 @@ int dg_read_batch(dg_context_t* ctx, const uint8_t* const* refs, const size_t* r
 		return DG_ERR_NOMEM;
 	}
 	for (uint32_t i = 0; i < n_streams; ++i) {
-		if (ref_len[i]) memcpy(h_ref.data() + sv[i].ref_off, refs[i], ref_len[i]);
+		if (packed[i]) memcpy(h_ref.data() + sv[i].ref_off, refs[i], packed[i]);
 		if (delta_len[i]) memcpy(h_delta.data() + sv[i].delta_off, deltas[i], delta_len[i]);
 	}
 	if (d_ref.alloc_nonnull(rt) || d_delta.alloc_nonnull(dt) || d_req.alloc_nonnull(sizeof(RdReq) * n_req) ||
@@ -251,8 +270,8 @@ int dg_read_batch(dg_context_t* ctx, const uint8_t* const* refs, const size_t* r
 		return ctx_fail(ctx, DG_ERR_HIP, "upload failed");
 	rc = dg_read_plan_index(plan, d_delta.as<uint8_t>(), nullptr, nullptr, nullptr, st);
 	if (rc) return rc;
-	rc = dg_read_plan_run(plan, d_ref.as<uint8_t>(), d_delta.as<uint8_t>(), d_req.as<dg_read_req_t>(), n_req,
-	                      d_out.as<uint8_t>(), d_len.as<uint32_t>(), d_st.as<int32_t>(), st);
+	rc = ops.run(plan, d_ref.as<uint8_t>(), d_delta.as<uint8_t>(), d_req.as<dg_read_req_t>(), n_req, d_out.as<uint8_t>(),
+	             d_len.as<uint32_t>(), d_st.as<int32_t>(), st);
 	if (rc) return rc;
 	if (hipMemcpyAsync(lens.data(), d_len.p, 4ull * n_req, hipMemcpyDeviceToHost, st) != hipSuccess ||
 	    hipMemcpyAsync(stv.data(), d_st.p, 4ull * n_req, hipMemcpyDeviceToHost, st) != hipSuccess ||
@@ -282,5 +301,3 @@ int dg_read_batch(dg_context_t* ctx, const uint8_t* const* refs, const size_t* r
 	}
 	return bs.result();
 }
-
-}  // extern "C"

@@ -132,17 +132,11 @@ extern "C" __global__ __launch_bounds__(kUpBlock) __attribute__((amdgpu_waves_pe
 	const uint32_t i = blockIdx.x;
 	if (i >= a.n) return;
 	const uint32_t tid = threadIdx.x, wave = tid >> 6;
-	__shared__ __attribute__((aligned(16))) uint8_t win[kDecWin + 32];
-	__shared__ __attribute__((aligned(16))) uint16_t N1[kDecWin];
-	__shared__ __attribute__((aligned(16))) uint16_t NX[3 * kDecWin];
-	__shared__ uint16_t cmds[kDecMaxCmds];
-	__shared__ uint16_t jumps[kDecMaxCmds / 16 + 2];
-	__shared__ uint32_t sh[8];
-	__shared__ uint32_t bsum[2 * (kDecMaxCmds / 64 + 1)];
+	__shared__ DecLdsMem M;
 	__shared__ uint64_t cpart[kDecWaves];
 	__shared__ uint32_t clast[kDecWaves];
 	__shared__ uint64_t cres;
-	const DecLds L = dec_lds(win, N1, NX, cmds, jumps, sh, bsum);
+	const DecLds L = dec_lds(M);
 
 #ifdef DG_UPDATE_PROF
 	uint64_t uprof[kUpProfN] = {};
@@ -201,7 +195,7 @@ extern "C" __global__ __launch_bounds__(kUpBlock) __attribute__((amdgpu_waves_pe
 						    make_uint4((uint32_t)w.next_pos, (uint32_t)(w.next_pos >> 32), w.cnt,
 						               (w.done ? kUpRecDone : 0u) | (w.free_win ? kUpRecFree : 0u));
 					uint16_t* q = reinterpret_cast<uint16_t*>(SC + sc_used + 16);
-					for (uint32_t k = tid; k < w.cnt; k += kUpBlock) q[k] = cmds[k];
+					for (uint32_t k = tid; k < w.cnt; k += kUpBlock) q[k] = M.cmds[k];
 					sc_used += rec;
 					++sc_wins;
 				} else {
@@ -219,7 +213,7 @@ extern "C" __global__ __launch_bounds__(kUpBlock) __attribute__((amdgpu_waves_pe
 	if (!st && a.crc_check) {
 		DecodeArgs da{};
 		da.tables = a.tables;
-		const DecCrc ct = dec_crc_tables(NX, da);
+		const DecCrc ct = dec_crc_tables(M.NX, da);
 		__syncthreads();
 		if (up_span_crc(ct, a.tables, (uintptr_t)O, rl, cpart, clast, &cres) != be64(D + 9)) st = 9;
 		__syncthreads();   // the tables' LDS is the parse's next
@@ -264,9 +258,9 @@ extern "C" __global__ __launch_bounds__(kUpBlock) __attribute__((amdgpu_waves_pe
 				cnt = umin32(uni(h.z), kDecMaxCmds);
 				free_win = uni(h.w) & kUpRecFree;
 				next_pos = ((uint64_t)uni(h.y) << 32) | uni(h.x);
-				shf = dec_load_window(win, D, dl, pos);
+				shf = dec_load_window(M.win, D, dl, pos);
 				const uint16_t* q = reinterpret_cast<const uint16_t*>(SC + used + 16);
-				for (uint32_t k = tid; k < cnt; k += kUpBlock) cmds[k] = q[k];
+				for (uint32_t k = tid; k < cnt; k += kUpBlock) M.cmds[k] = q[k];
 				__syncthreads();
 				used += up_rec_bytes(cnt);
 				++r;
@@ -282,15 +276,15 @@ extern "C" __global__ __launch_bounds__(kUpBlock) __attribute__((amdgpu_waves_pe
 			}
 			UPROF_ADD(UP_B_PARSE, tb1);
 			UPROF_T(tb2);
-			const uint8_t* wp = win + shf;
+			const uint8_t* wp = M.win + shf;
 			if (free_win) {
 				const uint32_t nb = (cnt + 63) / 64;
 				for (uint32_t b = wave; b < nb; b += kDecWaves) {
-					const DecCmd c = dec_cmd(wp, cmds, 64 * b, cnt, pos);
+					const DecCmd c = dec_cmd(wp, M.cmds, 64 * b, cnt, pos);
 					dec_flat_batch(c, true, O, O, D, L.xs);
 				}
 			} else {
-				dec_grouped_window(wp, cmds, cnt, pos, true, O, O, D, L.grp);
+				dec_grouped_window(wp, M.cmds, cnt, pos, true, O, O, D, L.grp);
 			}
 			block_sync_global();   // the window's stores complete before the next window
 			UPROF_ADD(UP_B_APPLY, tb2);
@@ -305,7 +299,7 @@ extern "C" __global__ __launch_bounds__(kUpBlock) __attribute__((amdgpu_waves_pe
 		block_sync_global();   // every wave's stores before any CRC read
 		DecodeArgs da{};
 		da.tables = a.tables;
-		const DecCrc ct = dec_crc_tables(NX, da);
+		const DecCrc ct = dec_crc_tables(M.NX, da);
 		__syncthreads();
 		if (up_span_crc(ct, a.tables, (uintptr_t)O, vsize, cpart, clast, &cres) != be64(D + 17)) cst = 10;
 	}
