@@ -38,9 +38,10 @@
 //
 // Under a stale index the walk re-checks what it relies on: every command of
 // a window starts where the one before it ends, an item starts inside the
-// bytes its window tiles, a window moves the item forward, and dec_window
-// re-checks every dst + len <= version_size and every COPY's src + len <=
-// ref_len.  Any violation ends the request with DG_ERR_MALFORMED.  Stores go
+// bytes its window tiles (or where a window of zero-length commands stands), a
+// window moves the item forward in the version or in the stream, and
+// dec_window re-checks every dst + len <= version_size and every COPY's
+// src + len <= ref_len.  Any violation ends the request with DG_ERR_MALFORMED.  Stores go
 // to [out_off, out_off + n) only: an item's range is clipped from its
 // parent's, and its out_base moves with it.
 #include <hip/hip_runtime.h>
@@ -211,7 +212,10 @@ extern "C" __global__ __launch_bounds__(kLnBlock) void dg_lineage_read_kernel(Ln
 			const uint4 it = stk[at];
 			const uint32_t lo = uni(it.x), hi = uni(it.y), ob = uni(it.z);
 			const bool inside = lo >= wfirst && lo < wend;
-			if (g == 0 && !inside) {
+			// a window of zero-length commands only, where the item starts, holds no byte of V: the top item
+			// moves on in the stream (its continuation: the same range at the next window)
+			const bool hollow = wfirst == wend && lo == wend;
+			if (g == 0 && !inside && !hollow) {
 				bad = true;   // the walk covers [lo, ...: (stale index)
 				break;
 			}

@@ -1389,7 +1389,9 @@ int dg_read_lineage(const uint8_t *r, size_t r_len,
  * index included, a run reads only reference and delta bytes of the plan's
  * streams and writes only inside the requests' slots.  Under a stale index the
  * kernel re-checks that the commands it walks follow one another and cover the
- * range, every COPY's src + len <= ref_len, and the depth; a violation ends
+ * range (a window of zero-length commands only covers nothing and is passed:
+ * the walk moves on in the stream), every COPY's src + len <= ref_len, and the
+ * depth; a violation ends
  * the request with DG_ERR_MALFORMED (bytes inside its slot are then
  * unspecified), so a request cannot fan out.
  *

@@ -30,6 +30,15 @@ so a family that silently shrinks fails).  What a limit excludes:
 No case asks a one-block kernel to move more than 1 MiB: outputs of compose,
 invert and splice carry a few KiB of literals, every read request is at most
 1 MiB after clipping (checked when the corpus is built).
+
+  * lineage: a level on R is bound as read is.  A level on another version has
+    that version's size as its ref_len, up to 2^32 - 1, so its src, src + len
+    and ref_len reach all of E ("inner" rows of ALLOWED): the one consumer that
+    takes a COPY's end, and a work item's hi, to 0xFFFFFFFF.  No level between R
+    and the requested one is ever built, on the host or the device.  Every
+    request is at most 1 MiB after clipping, resolves to at most 4096 leaf
+    pieces (sm.lineage_pieces) and lies at most 64 levels above R: bounds on
+    work, asserted when the corpus is built.
 """
 from __future__ import annotations
 
@@ -38,7 +47,7 @@ import struct
 
 import sparse_model as sm
 
-OK, UNSUPPORTED, TOO_LARGE, MALFORMED = sm.OK, sm.UNSUPPORTED, sm.TOO_LARGE, sm.MALFORMED
+OK, INVALID_ARG, UNSUPPORTED, TOO_LARGE, MALFORMED = sm.OK, sm.INVALID_ARG, sm.UNSUPPORTED, sm.TOO_LARGE, sm.MALFORMED
 H = 1 << 31
 U32 = 1 << 32
 E = [H - 1, H, H + 1, U32 - 2, U32 - 1]
@@ -56,6 +65,12 @@ ALLOWED = {
     "splice": {"src": LOW, "dst": LOW, "src+len": LOW, "dst+len": LOW, "version_size": LOW, "ref_len": LOW},
     "decode": {"src": LOW, "dst": [], "src+len": LOW, "dst+len": [], "version_size": [], "ref_len": LOW},
     "update": {"src": LOW, "dst": [], "src+len": LOW, "dst+len": [], "version_size": [], "ref_len": LOW},
+    # src, src+len, ref_len: of the levels on R; "inner ...": of the levels on another version, whose ref_len is the
+    # parent's version_size and so not bound by R; off, off+n: of the requests, on the requested level, n clipped
+    "lineage": {"src": LOW, "dst": E, "src+len": LOW, "dst+len": E, "version_size": E, "ref_len": LOW,
+                "inner src": E, "inner src+len": E, "inner ref_len": E, "off": E, "off+n": E,
+                # off of a request of at least one byte on a level whose index has "nothing follows" entries
+                "off beside dst 0xFFFFFFFF entries": E[:4]},
 }
 
 
@@ -462,6 +477,242 @@ def update_cases():
     return out
 
 
+# ── lineage: (name, nodes, requests, statuses) ──
+#
+# nodes: (ref_len or None, delta, parent or BASE, stated ref_len or None): a base level reads R.head(ref_len), any
+# other the version of nodes[parent]; a stated ref_len is what a device descriptor claims instead of the parent's
+# size (such a case has no host form).  requests: (node, off, length).  statuses: per node, as the contract of
+# include/delta_gpu.h gives them; the model must arrive at the same ones on its own.
+
+BASE = 0xFFFFFFFF
+S = U32 - 1                  # the largest version_size, and the largest ref_len of an inner level
+WORK_ITEMS = 256             # dg_lineage_work_items(): the fan-out cases overflow a stack of that many
+LINEAGE_MAX_PIECES = 4096
+LINEAGE_MAX_DEPTH = 64
+
+
+def stated_ref_len(nodes, i):
+    """What stream i's descriptor states: as lineage_cases.stated_ref_len."""
+    ref_len, _, parent, stated = nodes[i]
+    if stated is not None:
+        return stated
+    if parent == BASE:
+        return ref_len
+    below = sm.Stream.of(nodes[parent][1])
+    return below.version_size if below.header else sm.NO_LIMIT
+
+
+def lineage_path(nodes, i):
+    """(ref_len of the base, [d_1 .. d_k], [stated ref_len or None per level]) of node i."""
+    chain = [i]
+    while nodes[chain[-1]][2] != BASE:
+        chain.append(nodes[chain[-1]][2])
+    chain.reverse()
+    assert len(chain) <= LINEAGE_MAX_DEPTH
+    return nodes[chain[0]][0], [nodes[k][1] for k in chain], [nodes[k][3] for k in chain]
+
+
+def host_expressible(case):
+    return all(n[3] is None for n in case[1])
+
+
+_heads = {}
+
+
+def r_head(ref_len):
+    if ref_len not in _heads:
+        _heads[ref_len] = R.head(ref_len)
+    return _heads[ref_len]
+
+
+def lineage_model(nodes, i, off, n):
+    """(status, leaf pieces) of one request, from the sparse model."""
+    ref_len, ds, stated = lineage_path(nodes, i)
+    return sm.lineage_leaves(r_head(ref_len), ds, off, n, stated)
+
+
+def base_tiling(e, size=S):
+    """A version of `size` bytes tiled with COPYs of R.head(e): R[0, e) first (src + len == ref_len), then
+    short COPYs whose src and src + len are the members of LOW that e allows, then long ones from R's first window."""
+    cmds = [("C", 0, e)] + [("C", x - 7, 7) for x in LOW if x <= e] + [("C", x, min(9, e - x)) for x in LOW if x < e]
+    at = seq(cmds)[1]
+    while at < size:
+        n = min(size - at, e - 12340)
+        cmds.append(("C", 12340, n))
+        at += n
+    return sstream(cmds)
+
+
+def shift_level(rng, k, size=S, m=3):
+    """One ADD of m bytes and one long COPY: the ADD in front for even k (src + len == size - m), behind for odd
+    k (src + len == size, the parent's last byte)."""
+    return sstream([("A", rng.randbytes(m)), ("C", 0, size - m)] if k % 2 == 0 else [("C", m, size - m), ("A", rng.randbytes(m))])
+
+
+def inner_edges(rng):
+    """A version of 2^32 - 1 bytes whose COPYs put src and src + len on every member of E, against a parent of
+    2^32 - 1 bytes; a zero-length COPY reads at src = 0xFFFFFFFF."""
+    cmds = [("C", H - 1, 1), ("A", rng.randbytes(2)), ("C", H, 1), ("C", H + 1, 1), ("C", U32 - 2, 1), ("C", U32 - 1, 0),
+            ("C", U32 - 9, 7), ("A", rng.randbytes(1)), ("C", 0, H - 1)]
+    at = seq(cmds)[1]
+    cmds.append(("C", H - 40, S - at))
+    placed, size = seq(cmds)
+    srcs, ends = {c[1] for c in placed if c[0] == "C"}, {c[1] + c[3] for c in placed if c[0] == "C"}
+    assert size == S and set(E) <= srcs and set(E) <= ends and max(ends) == S
+    return stream(placed, size)
+
+
+def has_sentinel(d):
+    """The stream's index ends with entries for "nothing follows" (stream offset, dst = 0xFFFFFFFF): a stride of
+    1024 stream bytes begins after the last command's first byte."""
+    at = last = 25
+    for kind, _, _, n in sm.Stream.of(d).cmds:
+        last = at
+        at += 13 if kind == 1 else 9 + n
+    return len(d) // 1024 > last // 1024
+
+
+def _carried(nodes, i, memo):
+    """The command boundaries of node i's version: its own, and those of the levels below carried through its COPYs."""
+    if i not in memo:
+        import bisect
+        st = sm.Stream.of(nodes[i][1])
+        out = {c[2] for c in st.cmds}
+        if nodes[i][2] != BASE and st.header:
+            below = _carried(nodes, nodes[i][2], memo)
+            for kind, src, dst, n in st.cmds:
+                if kind == 1:
+                    out.update(dst + (b - src) for b in below[bisect.bisect_right(below, src):bisect.bisect_left(below, src + n)])
+        memo[i] = sorted(out)
+    return memo[i]
+
+
+def carried_bounds(nodes, i):
+    return _carried(nodes, i, {})
+
+
+def _lineage_requests(nodes, i, memo, extra=()):
+    """Around command boundaries of node i's version, its own and the carried ones (all of them up to 64, else
+    the first few, and the first, last and middle ones at or above 2^31 - 1), on E, and at the version's edges."""
+    vs = sm.Stream.of(nodes[i][1]).version_size
+    bounds = _carried(nodes, i, memo)
+    high = [b for b in bounds if b >= H - 1]
+    picked = bounds if len(bounds) <= 64 else bounds[1:4] + high[:10] + high[-10:] + high[len(high) // 2:len(high) // 2 + 4]
+    seen, rs = set(), list(extra)
+    for b in picked:
+        if b not in seen:
+            seen.add(b)
+            rs += [(max(o, 0), n) for o, n in ((b - 1, 2), (b, 1), (b, 17), (b - 17, 34))]
+    rs += [(e, 40) for e in E] + [(e - 40, 81) for e in E] + [(e - 40, 40) for e in E]
+    rs += [(0, 64), (vs, 5), (max(vs - 1, 0), 1), (max(vs - 3, 0), 10), (max(vs - 100, 0), 0xFFFFFFFF), (U32 - 5, 100),
+           (0xFFFFFFFF, 0xFFFFFFFF), (0, 0), (H - 4096, 8192)]
+    return [(i, off, n) for off, n in rs]
+
+
+FAILING_REQUESTS = [(0, 16), (H, 1), (0, 0)]
+LINEAGE_EXPECTED = {}   # name: per request (status, bytes, leaf pieces), from the sparse model
+
+
+def lineage_cases():
+    rng = random.Random(0x2339)
+    out = []
+
+    def add(name, nodes, want, statuses=None, extra=None):
+        """want: the nodes that are requested; statuses: per node, OK unless stated."""
+        statuses = statuses or [OK] * len(nodes)
+        memo, reqs = {}, []
+        for i in want:
+            if statuses[i] == OK:
+                reqs += _lineage_requests(nodes, i, memo, (extra or {}).get(i, ()))
+            else:
+                reqs += [(i, off, n) for off, n in FAILING_REQUESTS]
+        out.append((name, nodes, reqs, statuses))
+
+    def chain(ref_len, deltas):
+        return [(ref_len if j == 0 else None, d, BASE if j == 0 else j - 1, None) for j, d in enumerate(deltas)]
+
+    # tall: every level's version is 2^32 - 1 bytes, one piece per level and request
+    for depth, e in zip((2, 4, 64), LOW):
+        nodes = chain(e, [base_tiling(e)] + [shift_level(rng, k) for k in range(1, depth)])
+        add(f"tall_{depth}", nodes, sorted({0, 1, depth // 2, depth - 1}))
+    # edges at every level: the closing zero-length COPY at dst 0xFFFFFFFF below and above other levels
+    pf, size = edges_full(rng)
+    pg, _ = edges_full(rng)
+    nodes = chain(RLEN, [base_tiling(RLEN), stream(pf, size), inner_edges(rng), shift_level(rng, 2), stream(pg, size),
+                         shift_level(rng, 3), inner_edges(rng)])
+    add("edges_at_every_level", nodes, range(7))
+    # the index's "nothing follows" entries (dst = 0xFFFFFFFF) beside requests above 2^31: strides of bytes after
+    # END, and the strides inside a last ADD's payload
+    tail = sstream([("C", 0, S - 3000), ("A", rng.randbytes(3000))])
+    nodes = chain(RLEN, [base_tiling(RLEN) + bytes(1500), stream(pf, size) + bytes(2100), tail, inner_edges(rng) + bytes(1024),
+                         shift_level(rng, 2) + bytes(5000)])
+    assert all(has_sentinel(n[1]) for n in nodes)
+    add("sentinel_entries", nodes, range(5))
+    # version_size, and with it the ref_len of the level above, on every member of E
+    for e in E:
+        mid = sstream([("C", 3, H - 2), ("C", 3, e - 1 - (H - 2)), ("A", rng.randbytes(1))])
+        add(f"version_{e:#x}", chain(RLEN, [base_tiling(RLEN), mid, sstream([("A", rng.randbytes(2)), ("C", 2, e - 2)])]), [1, 2])
+    # fan-out above 2^31: the first command at dst 2^31 on an index stride, a window edge, a chunk edge; node 1 is
+    # requested (its COPYs are children one level down) and node 2 reads through it (children of a child)
+    for t, n_small in ((EDGES[0], 420), (EDGES[1], 1000), (EDGES[2], 420), (25 + EDGES[1], 1000)):
+        d, _, vs = covering(rng, S, target=t, n_small=n_small)
+        nodes = chain(RLEN, [base_tiling(RLEN), d, shift_level(rng, 2, size=vs), shift_level(rng, 3, size=vs)])
+        wide = [(H - 40, 8192), (H, 8192), (H + 3, 1 << 14)]
+        add(f"fanout_{t}_{n_small}", nodes, [1, 2, 3], extra={1: wide, 2: wide, 3: wide})
+    # inner ref_len at the limit
+    top_s = sstream([("C", S - 1, 1), ("A", rng.randbytes(2)), ("C", 0, S - 3)])           # src + len == ref_len == 2^32 - 1
+    add("limit_served", chain(RLEN, [base_tiling(RLEN), top_s, sstream([("C", S - 2, 2), ("C", 0, S - 2)])]), [1, 2])
+    faulty = stream([("C", U32 - 16, 0, 16)], 16)                                          # src + len == 2^32
+    up16 = sstream([("C", 8, 8), ("C", 0, 8)])
+    add("limit_2p32_at1", chain(RLEN, [faulty, up16, up16]), [0, 1, 2], [MALFORMED] * 3)
+    add("limit_2p32_at2", chain(RLEN, [base_tiling(RLEN), faulty, up16]), [0, 1, 2], [OK, MALFORMED, MALFORMED])
+    add("limit_2p32_at3", chain(RLEN, [base_tiling(RLEN), shift_level(rng, 1), faulty]), [0, 1, 2], [OK, OK, MALFORMED])
+    add("limit_src_ffffffff_len_1", chain(RLEN, [base_tiling(RLEN), stream([("C", U32 - 1, 0, 1)], 1)]), [1], [OK, MALFORMED])
+    unordered = stream([("C", 0, 8, 8), ("C", 8, 0, 8)], 16)                               # valid, not sequential
+    add("limit_unordered_above_2p32", chain(RLEN, [base_tiling(RLEN), faulty, unordered]), [2], [OK, MALFORMED, UNSUPPORTED])
+    add("limit_2p32_above_unordered", chain(RLEN, [sstream([("C", H - 8, 16)]), unordered, faulty]), [1, 2],
+        [OK, UNSUPPORTED, MALFORMED])
+    short = sstream([("A", rng.randbytes(2)), ("C", 0, S - 3)])                            # a version of 2^32 - 2 bytes
+    nodes = chain(RLEN, [base_tiling(RLEN), short, shift_level(rng, 1, size=S - 1)])
+    nodes[1] = nodes[1][:3] + (S - 1,)                                                     # the parent has 2^32 - 1
+    add("limit_stated_one_below", nodes, [0, 1, 2], [OK, INVALID_ARG, INVALID_ARG])
+    nodes = chain(RLEN, [base_tiling(RLEN, size=S - 1), sstream([("C", 0, S - 1)])])
+    nodes[1] = nodes[1][:3] + (S,)                                                         # the parent has 2^32 - 2
+    add("limit_stated_one_above", nodes, [0, 1], [OK, INVALID_ARG])
+    for name, junk in (("other_magic", b"XLT\x03" + bytes(40)), ("ten_bytes", b"DLT\x03\x00\x00\x00\x00\x10\x00")):
+        reads_all = sstream([("C", U32 - 9, 8), ("C", U32 - 1, 0)])                        # inside 2^32 - 1: "no limit"
+        add(f"limit_no_header_{name}", chain(RLEN, [junk, reads_all]), [0, 1], [MALFORMED, MALFORMED])
+        add(f"limit_no_header_{name}_2p32", chain(RLEN, [junk, stream([("C", U32 - 8, 0, 8)], 8)]), [1], [MALFORMED, MALFORMED])
+    # trees: lineages that share a high inner level, requested in one launch
+    d, _, vs = covering(rng, S, target=EDGES[0], n_small=420)
+    nodes = chain(RLEN, [base_tiling(RLEN), stream(pf, size)])
+    nodes += [(None, d, 1, None), (None, shift_level(rng, 3), 1, None), (None, shift_level(rng, 2, size=vs), 2, None),
+              (None, inner_edges(rng), 1, None), (None, shift_level(rng, 2), 5, None)]
+    add("tree_on_edges", nodes, range(2, 7), extra={2: [(H - 40, 8192)], 4: [(H - 40, 8192)]})
+    # the bounds on work of the module docstring; what the model gives is kept for the tests
+    for name, nodes, reqs, statuses in out:
+        LINEAGE_EXPECTED[name] = exp = []
+        for i, off, n in reqs:
+            st, leaves = lineage_model(nodes, i, off, n)
+            assert st == statuses[i], (name, i, st)
+            assert sum(len(x) for x in leaves) <= sm.SLICE_MAX and len(leaves) <= LINEAGE_MAX_PIECES, (name, i, off, n)
+            exp.append((st, b"".join(leaves), len(leaves)))
+    return out
+
+
+def window_children(d, pos):
+    """The non-empty COPYs of the 4 KiB parse window of stream d that starts at the command at stream offset pos:
+    the children of one step of the lineage walk when d is not the level on the base."""
+    at, kids, seen = 25, 0, False
+    for kind, ref, dst, n in sm.Stream.of(d).cmds:
+        seen = seen or at == pos
+        if at >= pos and at + (13 if kind == 1 else 9) <= pos + 4096:
+            kids += kind == 1 and n > 0
+        at += 13 if kind == 1 else 9 + n
+    assert seen, "no command starts there"
+    return kids
+
+
 # ── the corpus, built once ──
 
 _cache = {}
@@ -470,7 +721,7 @@ _cache = {}
 def corpus():
     if not _cache:
         _cache.update(compose=compose_cases(), invert=invert_cases(), read=read_cases(), splice=splice_cases(),
-                      decode=decode_cases(), update=update_cases())
+                      decode=decode_cases(), update=update_cases(), lineage=lineage_cases())
     return _cache
 
 
@@ -488,7 +739,7 @@ def _fields(d, into, rebase=0):
 def reach():
     """Per operator and quantity, the values the accepted cases take."""
     c = corpus()
-    out = {op: {q: set() for q in QUANTITIES} for op in c}
+    out = {op: {q: set() for q in ALLOWED[op]} for op in c}
     for _, a, b, st in c["compose"]:
         if st == OK:
             _fields(a, out["compose"])
@@ -510,4 +761,20 @@ def reach():
                     if kind == 1:
                         into["src"].add(ref + sro - whole[0])
                         into["src+len"].add(ref + sro - whole[0] + n)
+    into = out["lineage"]
+    for _, nodes, reqs, statuses in c["lineage"]:
+        for i, (ref_len, d, parent, _) in enumerate(nodes):
+            if statuses[i] == OK:   # (every level below an accepted one is accepted)
+                mine = {q: set() for q in QUANTITIES}
+                _fields(d, mine)
+                mine["ref_len"].add(stated_ref_len(nodes, i))
+                for q in QUANTITIES:
+                    into[q if parent == BASE or q.startswith(("dst", "version")) else "inner " + q].update(mine[q])
+        for i, off, n in reqs:
+            if statuses[i] == OK:
+                vs = sm.Stream.of(nodes[i][1]).version_size
+                into["off"].add(off)
+                into["off+n"].add(off + (0 if off >= vs else min(n, vs - off)))
+                if off < vs and n and has_sentinel(nodes[i][1]):
+                    into["off beside dst 0xFFFFFFFF entries"].add(off)
     return out

@@ -326,6 +326,23 @@ def fragmenting_forest(orc):
     return [chain_forest("fragmenting", R, ds)]
 
 
+def zero_length_forest(orc):
+    """Runs of zero-length COPYs longer than a parse window, in sequence (each starts where the one before it
+    ends): whole windows that hold no byte of the version, at the requested level and at an inner one.  A
+    range that spans a run is served through continuations that move on in the stream and not in the version."""
+    rng = random.Random(0x11F3)
+    R = rng.randbytes(3000)
+    d1 = block_permutation(orc, rng, R, 100)
+    V1 = rc.model_version(R, d1)[1]
+    cmds = [("C", 5, 100), ("A", rng.randbytes(7))] + [("C", k % 50, 0) for k in range(1000)] + [("C", 900, 300)]
+    cmds += [("A", b"")] * 700 + [("A", rng.randbytes(9)), ("C", 0, 64)] + [("C", 3000, 0)] * 330 + [("C", 1200, 50)]
+    d2 = seq_stream(orc, V1, cmds)
+    V2 = rc.model_version(V1, d2)[1]
+    assert len(d2) > 5 * rc.WINDOW and MAX_COPIES_PER_WINDOW < 330
+    d3 = seq_stream(orc, V2, [("C", 50, 400), ("A", rng.randbytes(3)), ("C", 0, len(V2))])
+    return [chain_forest("zero_length_windows", R, [d1, d2, d3])]
+
+
 def failing_forests(orc):
     """Lineages of three deltas in which one, at each level in turn, fails."""
     rng = random.Random(0x11F1)
@@ -370,7 +387,7 @@ def corpus(dg, orc):
     if "all" not in _cache:
         cap = dg.lineage_work_items()
         forests = history_forests(dg, orc) + tree_forest(orc) + window_forests(orc) + dense_forest(orc, cap)
-        forests += fanout_forest(orc, cap) + fragmenting_forest(orc) + failing_forests(orc)
+        forests += fanout_forest(orc, cap) + fragmenting_forest(orc) + zero_length_forest(orc) + failing_forests(orc)
         rng = random.Random(0x11F2)
         out = []
         for f in forests:

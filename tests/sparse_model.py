@@ -18,6 +18,8 @@ tests/test_sparse_model_cpu.py pins it to the dense models on all their corpora.
                 in-place streams (memmove order, zeros in an uncovered tail:
                 src/c/apply.c:271-284, as update_cases.py restates it), by
                 tracing each byte back through the commands that wrote it;
+  lineage       a byte range of a version k deltas away from R, by recursion
+                over pieces: no level between R and the requested one is built;
   crc64 combine crc(X || Y) from crc(X), crc(Y) and |Y| in Python ints;
   statuses      each operator's contract, with every sum in unbounded ints.
 
@@ -171,7 +173,7 @@ class Stream:
 
     def __init__(self, d: bytes):
         self.data = d
-        self.bounds, self.monotone = {}, None
+        self.bounds, self.monotone, self.tiles_v, self.tiles = {}, None, None, None
         self.header = len(d) >= 25 and d[:4] == b"DLT\x03"
         self.framing = self.header
         self.inplace, self.version_size, self.cmds = False, 0, []
@@ -200,12 +202,15 @@ class Stream:
 
     def placed(self) -> bool:
         """Every dst is the sum of the earlier lengths, and they sum to version_size."""
-        at = 0
-        for _, _, dst, n in self.cmds:
-            if dst != at:
-                return False
-            at += n
-        return at == self.version_size
+        if self.tiles_v is None:
+            at, self.tiles_v = 0, True
+            for _, _, dst, n in self.cmds:
+                if dst != at:
+                    self.tiles_v = False
+                    break
+                at += n
+            self.tiles_v = self.tiles_v and at == self.version_size
+        return self.tiles_v
 
     def pieces(self):
         """The non-empty commands as pieces."""
@@ -457,3 +462,99 @@ def read(R, delta: bytes, off: int, length: int):
         return MALFORMED, b""
     n = 0 if off >= st.version_size else min(length, st.version_size - off)
     return OK, replay(R, delta, (off, off + n))
+
+
+# ── lineage reads ──
+
+NO_LIMIT = U32 - 1   # ref_len of a level whose parent has no readable header
+
+
+def index_status(st: Stream, ref_len: int):
+    """What the read plan's index pass reports for a stream with that ref_len."""
+    if not st.header:
+        return MALFORMED
+    if st.inplace:
+        return UNSUPPORTED
+    return OK if st.framing and _bounds_ok(st, ref_len) else MALFORMED
+
+
+def lineage_ref_lens(base_len: int, deltas, stated=None):
+    """ref_len per level (index 0: the delta on R): what a descriptor states where
+    stated[j] is not None, else len(R) for the first and the header version_size
+    of the level below for the others (NO_LIMIT below a level without a header)."""
+    out = []
+    for j, d in enumerate(deltas):
+        if stated is not None and stated[j] is not None:
+            out.append(stated[j])
+        elif j == 0:
+            out.append(base_len)
+        else:
+            below = Stream.of(deltas[j - 1])
+            out.append(below.version_size if below.header else NO_LIMIT)
+    return out
+
+
+def lineage_status(base_len: int, deltas, stated=None):
+    """The contract's order (include/delta_gpu.h): from the requested level
+    towards R, per level a. its index status with its ref_len, b. UNSUPPORTED if
+    it is not sequential, c. INVALID_ARG if its ref_len is not the version_size
+    of a level below whose own index status is 0 (stated descriptors only)."""
+    streams = [Stream.of(d) for d in deltas]
+    ref = lineage_ref_lens(base_len, deltas, stated)
+    for j in range(len(deltas) - 1, -1, -1):
+        st = index_status(streams[j], ref[j])
+        if st:
+            return st
+        if not streams[j].placed():
+            return UNSUPPORTED
+        if j and index_status(streams[j - 1], ref[j - 1]) == OK and ref[j] != streams[j - 1].version_size:
+            return INVALID_ARG
+    return OK
+
+
+def _tiling(st: Stream):
+    if st.tiles is None:
+        st.tiles = st.pieces()
+        st.tile_starts = [p[0] for p in st.tiles]
+    return st.tiles, st.tile_starts
+
+
+def _lineage_leaves(R, streams, j, lo, hi, out):
+    """Bytes [lo, hi) of V_j, lo < hi, as leaf pieces appended to out: an ADD
+    yields its payload, a COPY becomes [src, src + len) one level down, level 0
+    slices R."""
+    if j == 0:
+        out.append(R[lo:hi])
+        return
+    for _, n, kind, x in cut(*_tiling(streams[j - 1]), lo, hi):
+        if kind == "lit":
+            out.append(x)
+        else:
+            _lineage_leaves(R, streams, j - 1, x, x + n, out)
+
+
+def lineage_leaves(R, deltas, off: int, length: int, stated=None):
+    """(status, the leaf pieces of the request in output order: ADD payloads and slices of R)."""
+    R = SparseBytes.of(R)
+    status = lineage_status(len(R), deltas, stated)
+    if status:
+        return status, []
+    streams = [Stream.of(d) for d in deltas]
+    vs = streams[-1].version_size if streams else len(R)
+    n = 0 if off >= vs else min(length, vs - off)
+    out = []
+    if n:
+        _lineage_leaves(R, streams, len(streams), off, off + n, out)
+    return OK, out
+
+
+def lineage_read(R, deltas, off: int, length: int, stated=None):
+    """dg_read_lineage and dg_lineage_plan_run: (status, bytes [off, off + n) of
+    V_k) with pread's n; deltas[0] is the delta on R."""
+    status, leaves = lineage_leaves(R, deltas, off, length, stated)
+    return status, b"".join(leaves)
+
+
+def lineage_pieces(R, deltas, off: int, length: int, stated=None):
+    """The leaf pieces (ADD payloads and slices of R) the request resolves to."""
+    return len(lineage_leaves(R, deltas, off, length, stated)[1])

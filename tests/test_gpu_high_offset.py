@@ -11,7 +11,9 @@ run): ComposePlan and SplicePlan take theirs as they are; InvertPlan's and
 ReadPlan's are subclassed only to take their reference from the shared arena
 instead of building one from bytes.  DecodePlan and UpdatePlan are driven
 directly: the update harness downloads its whole buffer after a run, which here
-is the 4 GiB arena.  Decode and update run without CRC checks (one block would
+is the 4 GiB arena.  LineagePlan's harness is subclassed as ReadPlan's is: the
+levels on R name prefixes of the arena, the others state their parent's size.
+Decode and update run without CRC checks (one block would
 checksum 4 GiB); the decode_large test runs with them, on a version of
 2^31 + 2^20 + 3 bytes whose expected CRC comes from the model's combine.
 
@@ -31,6 +33,7 @@ import sparse_model as sm
 from test_gpu_compose import Run as ComposeRun
 from test_gpu_index_chunked import ChunkedRun
 from test_gpu_invert import Run as InvertBase
+from test_gpu_lineage import LineageRun
 from test_gpu_splice import Run as SpliceRun
 
 pytestmark = pytest.mark.gpu
@@ -296,3 +299,97 @@ def test_read_plan_limits(dg, ctx):
         p.chunk_index(4096)
     assert e.value.code == TOO_LARGE
     p.close()
+
+
+# 9. lineage: every case in one plan, every request; the one-block index, then the chunked index over it
+class HighLineageRun(LineageRun):
+    def __init__(self, torch, dg, ctx, d_ref, nodes, requests, sizes):
+        """nodes: (ref_len or None, delta, parent, stated ref_len or None); a level on R reads a prefix of d_ref."""
+        self.torch, self.dg, self.ctx, self.items, self.nodes = torch, dg, ctx, nodes, nodes
+        self.n = len(nodes)
+        dlt, self.streams = bytearray(), []
+        for k, (_, d, parent, _) in enumerate(nodes):
+            dlt += bytes([GUARD]) * ((1 + (3 * k) % 15) if k % 2 else (-len(dlt) % 16))
+            # (a level on another version: its ref_off is ignored, an odd one)
+            self.streams.append((0 if parent == hc.BASE else 12345, hc.stated_ref_len(nodes, k), len(dlt), len(d)))
+            dlt += d
+        self.d_ref = d_ref
+        self.d_delta = torch.frombuffer(dlt + b"\0", dtype=torch.uint8).cuda()
+        self.max_requests = len(requests)
+        self.plan = self.reads = dg.ReadPlan(ctx, self.streams, self.max_requests)
+        self.lin = dg.LineagePlan(self.reads, [n[2] for n in nodes], self.max_requests)
+        self.d_sst = torch.full((self.n,), -1, dtype=torch.int32, device="cuda")
+        self.set_requests(requests, sizes)
+
+    def check_model(self, expected, names):
+        """Run.check with the sparse model's results: every length and status, and the output arena compared whole."""
+        exp = self.before.copy()
+        for j, ((s, off, ln), (st, got, _)) in enumerate(zip(self.requests, expected)):
+            assert self.st[j] == st, (names[j], s, off, ln, self.st[j], st)
+            assert self.out_len[j] == len(got), (names[j], s, off, ln, self.out_len[j], len(got))
+            o, room = self.slots[j]
+            assert len(got) <= room
+            exp[o:o + len(got)] = np.frombuffer(got, dtype=np.uint8)
+        bad = np.flatnonzero(self.after != exp)
+        if bad.size:
+            at = int(bad[0])
+            j = max(k for k, (o, _) in enumerate(self.slots) if o - 64 <= at)
+            raise AssertionError(f"{bad.size} bytes differ, the first at {at}: {names[j]} {self.requests[j]}, "
+                                 f"slot at {self.slots[j]}, got {int(self.after[at])} want {int(exp[at])}")
+
+
+def _lineage_plan(cases):
+    """One forest of all cases: (nodes, requests, sizes, expected, case name per request)."""
+    nodes, reqs, sizes, expected, names = [], [], [], [], []
+    for name, ns, rs, sts in cases:
+        base = len(nodes)
+        nodes += [(rl, d, p if p == hc.BASE else p + base, stated) for rl, d, p, stated in ns]
+        for (i, off, ln), e in zip(rs, hc.LINEAGE_EXPECTED[name]):
+            reqs.append((base + i, off, ln))
+            sizes.append(0 if sts[i] else sm.Stream.of(ns[i][1]).version_size)
+            expected.append(e)
+            names.append(name)
+    return nodes, reqs, sizes, expected, names
+
+
+@pytest.mark.parametrize("chunk_bytes", [4096, 65536])
+def test_lineage_plan(dg, ctx, torch_cuda, arena, chunk_bytes):
+    cases = hc.corpus()["lineage"]
+    assert dg.lineage_work_items() == hc.WORK_ITEMS   # the fan-out cases are sized for it
+    nodes, reqs, sizes, expected, names = _lineage_plan(cases)
+    assert len(reqs) > 3500 and {e[0] for e in expected} == {OK, sm.INVALID_ARG, sm.UNSUPPORTED, sm.MALFORMED}
+    r = HighLineageRun(torch_cuda, dg, ctx, arena, nodes, reqs, sizes)
+    r.index().run()
+    r.check_model(expected, names)
+    first, st1, len1, sst1 = r.after.copy(), list(r.st), list(r.out_len), list(r.stream_st)
+    r.reset_out()
+    r.d_sst.fill_(-1)
+    r.reads.chunk_index(chunk_bytes)
+    r.reads.index_chunked(r.d_delta.data_ptr(), r.d_sst.data_ptr(), stream=ctx.stream)
+    r.run()
+    r.check_model(expected, names)
+    assert np.array_equal(r.after, first) and r.st == st1 and r.out_len == len1 and r.stream_st == sst1
+
+
+# 10. the host wrapper on a thinned set: one lineage tree, against dg_read_lineage.  The wrapper takes host bytes
+# and uploads them, so it cannot use the module's arena: one tree means one R, 4 GiB on the host and a second
+# 4 GiB on the device while the call lasts.  Measured on an MI355X: 2.2 s for the whole test.
+def test_read_lineage_batch_equals_read_lineage(dg, ctx, torch_cuda):
+    name, ns, rs, sts = next(c for c in hc.corpus()["lineage"] if c[0] == "tree_on_edges")
+    assert [n[0] for n in ns].count(hc.RLEN) == 1 and all(n[3] is None for n in ns)
+    buf = np.zeros(hc.RLEN, dtype=np.uint8)
+    for o, b in hc.R.windows():
+        buf[o:o + len(b)] = np.frombuffer(b, dtype=np.uint8)
+    host_r = buf.tobytes()
+    del buf
+    # (the wrapper sizes a slot by min(len, version_size): a length of 4 GiB on these versions would be a 4 GiB slot)
+    picked = [(q, e) for k, (q, e) in enumerate(zip(rs, hc.LINEAGE_EXPECTED[name]))
+              if q[2] <= 1 << 20 and (k % 4 == 0 or e[2] > 400)]   # (and every request of hundreds of pieces)
+    assert len(picked) > 100 and sum(1 for _, e in picked if e[2] > 400) >= 2
+    got, st = dg.read_lineage_batch([(host_r if n[0] else None, n[1]) for n in ns], [n[2] for n in ns], [q for q, _ in picked],
+                                    ctx=ctx, status=True)
+    torch_cuda.cuda.empty_cache()
+    for k, ((i, off, ln), e) in enumerate(picked):
+        assert (st[k], got[k]) == (e[0], e[1]), (i, off, ln)
+        if k % 8 == 0:
+            assert dg.read_lineage(host_r, hc.lineage_path(ns, i)[1], off, ln) == got[k], (i, off, ln)

@@ -118,6 +118,16 @@ def test_fragmenting(dg, ctx, orc, torch_cuda):
     assert sts == [OK] * 5 and len(r.requests) > 300
 
 
+# 3b. whole windows of zero-length commands: a continuation that moves on in the stream and not in the version
+def test_windows_of_zero_length_commands(dg, ctx, orc, torch_cuda):
+    f, per = lc.by_name(dg, orc, "zero_length_windows")
+    r, sts, vers = _run_cases(torch_cuda, dg, ctx, [(f, per)])
+    assert sts == [OK] * 3
+    for s in (1, 2):   # the whole version, through every run of them, from the level that has them and from above it
+        j = r.requests.index((s, 0, len(vers[s])))
+        assert r.st[j] == OK and r.out_len[j] == len(vers[s])
+
+
 # 4. the order of the statuses: every failing lineage beside served requests of the same launch
 def test_status_order(dg, ctx, orc, torch_cuda):
     cases = [c for c in lc.corpus(dg, orc) if c[0]["name"].startswith("fail_")]

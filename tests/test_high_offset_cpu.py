@@ -1,4 +1,4 @@
-"""CPU: the HIP-free host code (dg_compose, dg_invert, dg_read, dg_splice) on
+"""CPU: the HIP-free host code (dg_compose, dg_invert, dg_read, dg_read_lineage, dg_splice) on
 the high-offset corpus of tests/high_offset_cases.py, against the sparse model:
 exact bytes, exact statuses.
 
@@ -41,11 +41,11 @@ def _take(dg, rc_, out):
 def test_corpus_reaches_what_it_is_for():
     got = hc.reach()
     for op, want in hc.ALLOWED.items():
-        for q in hc.QUANTITIES:
+        for q in want:
             missing = [hex(x) for x in want[q] if x not in got[op][q]]
             assert not missing, (op, q, missing)
     c = hc.corpus()
-    assert all(len(c[k]) >= n for k, n in dict(compose=39, invert=30, read=35, splice=28, decode=13, update=16).items())
+    assert all(len(c[k]) >= n for k, n in dict(compose=39, invert=30, read=35, splice=28, decode=13, update=16, lineage=28).items())
     # the families: long single commands, merges above 2^31, 400 commands and more, the window and chunk edges
     big = [sm.Stream.of(x[1]) for x in c["compose"]] + [sm.Stream.of(x[2]) for x in c["invert"] + c["read"]]
     assert sum(1 for s in big if any(n >= hc.H for _, _, _, n in s.cmds)) >= 20
@@ -60,6 +60,39 @@ def test_corpus_reaches_what_it_is_for():
     one = next(x for x in c["splice"] if x[0] == "one_copy_65")
     assert [(k, n) for k, _, _, n in sm.Stream.of(sm.splice(*one[1:5])[1]).cmds] == [(1, hc.RLEN)]
     assert all(seg[3] < hc.H for seg in one[2])
+    # the lineage families
+    lin = {x[0]: x for x in c["lineage"]}
+    for depth in (2, 4, 64):   # tall: every level 2^32 - 1 bytes, the top one requested
+        _, nodes, reqs, sts = lin[f"tall_{depth}"]
+        assert len(nodes) == depth and sts == [sm.OK] * depth and any(i == depth - 1 for i, _, _ in reqs)
+        assert all(sm.Stream.of(n[1]).version_size == hc.S for n in nodes)
+        assert len(hc.lineage_path(nodes, depth - 1)[1]) == depth
+    _, nodes, reqs, sts = lin["edges_at_every_level"]
+    closing = [i for i, n in enumerate(nodes) if sm.Stream.of(n[1]).cmds[-1] == (1, 7, hc.S, 0)]
+    assert len(closing) == 2 and all(0 < i < len(nodes) - 1 for i in closing) and {i for i, _, _ in reqs} == set(range(7))
+    for i in range(7):   # every boundary straddled at the level that has it and, carried through the COPYs, from every level above
+        bounds = hc.carried_bounds(nodes, i)
+        assert i not in closing or set(hc.E) <= set(bounds)
+        assert i < closing[0] or sum(1 for b in bounds if b >= hc.H - 4) >= 5, i   # edges_full's, carried
+        assert all((i, b - 1, 2) in reqs and (i, b - 17, 34) in reqs for b in bounds if b >= 17), i
+    fan = [x for x in c["lineage"] if x[0].startswith("fanout_")]
+    assert sorted(int(x[0].split("_")[1]) for x in fan) == sorted(hc.EDGES + [25 + 4096]) and len(fan) == 4
+    for name, nodes, reqs, sts in fan:
+        t, n_small = (int(w) for w in name.split("_")[1:])
+        st = sm.Stream.of(nodes[1][1])
+        assert t % 1024 == 0 or (t - 25) % 4096 == 0, name
+        assert len(hc.stream([], 0, end=False)) == 25 and sum(1 for c_ in st.cmds if c_[2] >= hc.H) > n_small
+        kids = hc.window_children(nodes[1][1], t)   # the window the index enters for lo = 2^31
+        assert kids > hc.WORK_ITEMS, (name, kids)   # more children than the stack has slots: the item is cut above 2^31
+        assert all((i, hc.H, 8192) in reqs for i in (1, 2, 3)), name
+    assert {n_small for n_small in (420, 1000)} == {int(x[0].split("_")[2]) for x in fan}
+    limit = [x for x in c["lineage"] if x[0].startswith("limit_")]
+    assert len(limit) >= 13 and sum(1 for x in limit if not hc.host_expressible(x)) == 2
+    assert [lin[f"limit_2p32_at{k}"][3].index(sm.MALFORMED) for k in (1, 2, 3)] == [0, 1, 2]
+    assert lin["limit_served"][3] == [sm.OK] * 3
+    _, nodes, reqs, sts = lin["tree_on_edges"]
+    assert [n[2] for n in nodes].count(1) == 3 and {i for i, _, _ in reqs} == {2, 3, 4, 5, 6} and sts == [sm.OK] * 7
+    assert max(e[2] for v in hc.LINEAGE_EXPECTED.values() for e in v) > 1000   # (leaf pieces of one request)
     # R: windows at and around 2^31, at odd offsets, and at the last byte
     assert all(o % 2 for o, _ in hc.R.windows()) and hc.R[hc.RLEN - 1:hc.RLEN] != b"\0" and len(hc.R) == sm.PLAN_LIMIT - 1
     assert hc.R[hc.H - 2:hc.H + 2].count(0) < 3
@@ -82,6 +115,10 @@ def test_the_model_gives_the_stated_statuses():
         assert sm.decode_status(ref_len, d, 65536) == st, name
     for name, ref_len, d, st in c["update"]:
         assert sm.update_status(ref_len, d, hc.RLEN) == st, name
+    for name, nodes, reqs, sts in c["lineage"]:
+        for i in {i for i, _, _ in reqs}:
+            ref_len, ds, stated = hc.lineage_path(nodes, i)
+            assert sm.lineage_status(ref_len, ds, stated) == sts[i], (name, i)
     # no one-block kernel moves more than 1 MiB, and no output exceeds 64 KiB of literals by much
     for name, a, b, st in c["compose"]:
         assert len(sm.compose(a, b)[1]) < 65536 + 4096, name
@@ -115,6 +152,27 @@ def test_dg_read(dg, host_r):
             rc_ = dg.lib.dg_read(host_r.ctypes.data_as(U8P), ref_len, dg._lib._u8(d), len(d), off, n, C.byref(out))
             assert _take(dg, rc_, out) == sm.read(ref, d, off, n), (name, off, n)
             assert rc_ == st, name
+
+
+def test_dg_read_lineage(dg, host_r):
+    """Every case the host can express (no stated ref_len), every request: the status and the bytes of the model."""
+    assert dg.lineage_work_items() == hc.WORK_ITEMS   # the fan-out cases are sized for it
+    ran = 0
+    for case in hc.corpus()["lineage"]:
+        name, nodes, reqs, sts = case
+        if not hc.host_expressible(case):
+            continue
+        for (i, off, n), (st, exp, _) in zip(reqs, hc.LINEAGE_EXPECTED[name]):
+            ref_len, ds, _ = hc.lineage_path(nodes, i)
+            k = len(ds)
+            dp = (U8P * k)(*[dg._lib._u8(d) for d in ds])
+            dl = (C.c_size_t * k)(*[len(d) for d in ds])
+            out = dg._lib.Buffer()
+            rc_ = dg.lib.dg_read_lineage(host_r.ctypes.data_as(U8P), ref_len, dp, dl, k, off, n, C.byref(out))
+            assert _take(dg, rc_, out) == (st, exp), (name, i, off, n)
+            assert rc_ == sts[i], (name, i)
+            ran += 1
+    assert ran > 3500
 
 
 def test_dg_splice(dg):

@@ -94,6 +94,45 @@ def test_read_equals_the_dense_model(dg, orc):
     assert n > 10000
 
 
+def test_lineage_read_equals_the_dense_model(dg, orc):
+    """Every forest of lineage_cases whose statuses the host can express (a
+    stated ref_len that is not the parent's size exists on the device only; those
+    forests are pinned to lineage_cases.node_status instead), every node, every
+    range: lc.model_lineage_read's status and bytes.  The dense model rebuilds
+    every level per call, so it is called once per node (and for every range of a
+    failing one); the other ranges are slices of the version it built, which
+    lineage_cases.resolve keeps."""
+    import lineage_cases as lc
+    n = stated = 0
+    for f, per in lc.corpus(dg, orc):
+        nodes = f["nodes"]
+        for i, (st, V, rs) in enumerate(per):
+            R, ds = lc.path(nodes, i)
+            refs = None
+            if f.get("host", True):
+                for off, ln in rs if st else rs[:1]:
+                    assert sm.lineage_read(R, ds, off, ln) == lc.model_lineage_read(R, ds, off, ln), (f["name"], i, off, ln)
+            else:
+                chain = [i]
+                while nodes[chain[-1]][2] != lc.BASE:
+                    chain.append(nodes[chain[-1]][2])
+                refs = [nodes[k][3] for k in chain[::-1]]
+                stated += st == sm.INVALID_ARG
+            for off, ln in rs:
+                want = (st, b"") if st else (sm.OK, rc.model_read(V, off, ln))
+                assert sm.lineage_read(R, ds, off, ln, stated=refs) == want, (f["name"], i, off, ln)
+                n += 1
+            assert st or sm.lineage_pieces(R, ds, 0, len(V), stated=refs) >= (len(V) > 0)
+    assert n > 3000 and stated >= 4
+    # a piece count by hand: 3 bytes of payload, then 2 pieces of R through a level that cuts the range once
+    R = bytes(range(200))
+    import high_offset_cases as hc
+    d1 = hc.sstream([("C", 100, 50), ("C", 0, 50)])
+    d2 = hc.sstream([("A", b"abc"), ("C", 40, 30)])
+    assert sm.lineage_read(R, [d1, d2], 0, 99) == (sm.OK, b"abc" + R[140:150] + R[0:20])
+    assert sm.lineage_pieces(R, [d1, d2], 0, 99) == 3 and sm.lineage_pieces(R, [d1, d2], 3, 10) == 1
+
+
 def test_replay_equals_the_oracle_on_inplace_streams(dg, orc):
     """update_cases' families, in-place: memmove order, overwrites, zeros in an
     uncovered grown tail.  Read whole and as three windows."""
