@@ -437,8 +437,9 @@ extern "C" __global__ __launch_bounds__(256) void dg_inplace_emit_kernel(IpArgs 
 	const uint8_t* D = a.delta + res.stream_off;
 	uint8_t* O = a.out + base;
 	if (res.passthrough) {
-		for (uint32_t c = wave * 4096u; c < res.stream_len; c += 4 * 4096u)
-			wave_copy(O + c, D + c, umin32(4096u, res.stream_len - c), lane);
+		// (64-bit: a stream may be up to 2^32 - 1 bytes, and a 32-bit counter would wrap above 2^32 - 16384)
+		for (uint64_t c = wave * 4096u; c < res.stream_len; c += 4 * 4096u)
+			wave_copy(O + c, D + c, umin32(4096u, (uint32_t)(res.stream_len - c)), lane);
 		return;
 	}
 	const IpDesc dd = a.descs[i];

@@ -489,6 +489,12 @@ int dg_encode_commands(const dg_placed_command_t *cmds, size_t n, int inplace,
  * -> delta_make_inplace(policy) -> delta_encode(inplace = true), byte for
  * byte.  A delta that is already in-place is returned unchanged
  * (stats->already_inplace = 1).  Pure host code: no context, no GPU.
+ * Like the reference it does not take the dst fields as they are: it sorts
+ * the commands by dst (stable) and places them one after the other itself, in
+ * 64 bits.  So a stream whose dst fields are off by some bytes, or whose
+ * lengths sum past 2^32 (every dst field then being the running sum mod 2^32),
+ * is converted all the same: DG_OK, the output's dst fields being the new
+ * places mod 2^32.  The device plan refuses both (DG_ERR_UNSUPPORTED, below).
  * dg_encode / dg_encode_batch with DG_OPT_INPLACE (policy from
  * dg_diff_options_t.flags bit DG_OPT_POLICY_CONSTANT) run this on their
  * output; dg_encode_pipelined with DG_OPT_INPLACE and dg_make_inplace_batch

@@ -39,6 +39,10 @@ invert and splice carry a few KiB of literals, every read request is at most
     request is at most 1 MiB after clipping, resolves to at most 4096 leaf
     pieces (sm.lineage_pieces) and lies at most 64 levels above R: bounds on
     work, asserted when the corpus is built.
+  * inplace: the victims read R, so src, src + len and ref_len are bound as invert's are.  The expected bytes
+    are the reference's own (tests/golden/golden_inplace_high.json) and dg_make_inplace's, not the model's; no
+    expected output holds more than 1 MiB of victim payload under the policy it is listed for (asserted when the
+    corpus is built, from the CRWI digraph of each stream), but for the capacity cases, which nothing converts.
 """
 from __future__ import annotations
 
@@ -62,6 +66,7 @@ ALLOWED = {
     "compose": {"src": E, "dst": E, "src+len": E + [U32], "dst+len": E, "version_size": E, "ref_len": []},
     "invert": {"src": LOW, "dst": E, "src+len": LOW, "dst+len": E, "version_size": E, "ref_len": LOW},
     "read": {"src": LOW, "dst": E, "src+len": LOW, "dst+len": E, "version_size": E, "ref_len": LOW},
+    "inplace": {"src": LOW, "dst": E, "src+len": LOW, "dst+len": E, "version_size": E, "ref_len": LOW},
     "splice": {"src": LOW, "dst": LOW, "src+len": LOW, "dst+len": LOW, "version_size": LOW, "ref_len": LOW},
     "decode": {"src": LOW, "dst": [], "src+len": LOW, "dst+len": [], "version_size": [], "ref_len": LOW},
     "update": {"src": LOW, "dst": [], "src+len": LOW, "dst+len": [], "version_size": [], "ref_len": LOW},
@@ -128,7 +133,7 @@ def edges_full(rng):
     return placed, size
 
 
-def covering(rng, ref_len, target=None, n_small=420):
+def covering(rng, ref_len, target=None, n_small=420, top=H):
     """A sequentially placed stream that reads nearly all of R[0, ref_len): what
     invert needs to keep its literals small, and a fair stream for every other
     operator.  One COPY up to V offset 2^31 exactly; then n_small short commands,
@@ -137,14 +142,15 @@ def covering(rng, ref_len, target=None, n_small=420):
     one byte before R's end.  With target, the first command at dst 2^31 starts at
     that stream offset: 1-byte COPYs of consecutive sources (which merge) and one
     ADD pad the stream in front of the long COPY.  n_small = 1000 makes a stream
-    of more than three 4 KiB chunks."""
+    of more than three 4 KiB chunks.  top: another V offset than 2^31 for the
+    long COPY's end, for a ref_len too short for sources above 2^31."""
     n_pad, fine = 0, 3
     if target is not None:
         n_pad = (target - 47 - 1) // 13
         fine = target - 47 - 13 * n_pad
         assert 1 <= fine <= 13
-    cmds = [("C", k, 1) for k in range(n_pad)] + [("A", rng.randbytes(fine)), ("C", n_pad, H - n_pad - fine)]
-    at_r = H - fine                      # R is read up to here
+    cmds = [("C", k, 1) for k in range(n_pad)] + [("A", rng.randbytes(fine)), ("C", n_pad, top - n_pad - fine)]
+    at_r = top - fine                      # R is read up to here
     small = []
     for k in range(n_small):
         at_r += rng.randint(0, 3) if k % 5 else 0
@@ -161,8 +167,8 @@ def covering(rng, ref_len, target=None, n_small=420):
     placed, size = seq(cmds)
     d = stream(placed, size)
     if target is not None:
-        first_high = next(k for k, c in enumerate(placed) if c[1 if c[0] == "A" else 2] >= H)
-        assert len(stream(placed[:first_high], 0, end=False)) == target and placed[first_high][2] == H
+        first_high = next(k for k, c in enumerate(placed) if c[1 if c[0] == "A" else 2] >= top)
+        assert len(stream(placed[:first_high], 0, end=False)) == target and placed[first_high][2] == top
     assert size < U32 and at_r < ref_len - 1
     return d, placed, size
 
@@ -713,7 +719,307 @@ def window_children(d, pos):
     return kids
 
 
-# ── the corpus, built once ──
+# ── in-place conversion: (name, ref_len, standard delta, statuses) ──
+#
+# statuses: {"localmin": ..., "constant": ..., "host": ...}: what the device plan gives under each policy, and
+# what dg_make_inplace returns.  A case without a policy's key is not in that policy's list: the constant policy
+# converts the lowest-index pending copy whatever its length, which in a covering() stream is the one of 2 GiB.
+# The expected bytes are not computed here: they are the reference's own (tests/golden/golden_inplace_high.json)
+# and, as a second comparator, dg_make_inplace's.  What is computed here is the CRWI digraph of a stream, as
+# dg_inplace.cpp builds it, for the bounds on work and for the sizes of the capacity cases.
+
+POLICIES = ("localmin", "constant")
+IP_LENGTHS = [1, 7, 255, 256, 256, 257, 65535, 65536, 65537, (1 << 24) - 1, 1 << 24, 1 << 24, (1 << 24) + 1,
+              (1 << 24) + 256, 3 << 24, 1 << 30, H - (1 << 20) - 1]      # both sides of every radix byte, with ties
+IP_WINDOWS = [H - 33, H + 100001, 3 * (1 << 30) + 5]                     # the windows of R the cycles' blocks read
+IP_VICTIM_MAX = 1 << 20
+IP_VICTIMS = {}              # name of a touching case: the victims it was built for (the same under both policies)
+
+
+def copies_of(d):
+    return [(src, dst, n) for kind, src, dst, n in sm.Stream.of(d).cmds if kind == 1]
+
+
+def crwi_ranges(copies):
+    """Per copy i the index range [a, b) of the copies whose writes its read interval meets (i itself may lie
+    inside and is no neighbour): dg_inplace.cpp step 3, for commands placed sequentially (dst non-decreasing)."""
+    import bisect
+    starts = [c[1] for c in copies]
+    assert starts == sorted(starts)
+    out = []
+    for i, (src, _, n) in enumerate(copies):
+        lo = bisect.bisect_left(starts, src)
+        hi = bisect.bisect_left(starts, src + n, lo)
+        if lo > 0 and lo - 1 != i and copies[lo - 1][1] + copies[lo - 1][2] > src:
+            lo -= 1
+        out.append((lo, hi))
+    return out
+
+
+def has_edges(copies):
+    return any(b - a > (1 if a <= i < b else 0) for i, (a, b) in enumerate(crwi_ranges(copies)))
+
+
+def crwi_sccs(copies):
+    """The non-trivial strongly connected components of the CRWI digraph (Tarjan, iterative)."""
+    n, rs = len(copies), crwi_ranges(copies)
+    index, low, on, stack, comps, counter = [None] * n, [0] * n, [False] * n, [], [], 0
+    for s in range(n):
+        if index[s] is not None:
+            continue
+        index[s] = low[s] = counter
+        counter += 1
+        on[s] = True
+        stack.append(s)
+        call = [[s, rs[s][0]]]
+        while call:
+            v, x = call[-1]
+            if x == v:
+                x += 1
+            if x < rs[v][1]:
+                call[-1][1] = x + 1
+                if index[x] is None:
+                    index[x] = low[x] = counter
+                    counter += 1
+                    on[x] = True
+                    stack.append(x)
+                    call.append([x, rs[x][0]])
+                elif on[x]:
+                    low[v] = min(low[v], index[x])
+                continue
+            call.pop()
+            if call:
+                low[call[-1][0]] = min(low[call[-1][0]], low[v])
+            if low[v] == index[v]:
+                comp = []
+                while True:
+                    x = stack.pop()
+                    on[x] = False
+                    comp.append(x)
+                    if x == v:
+                        break
+                if len(comp) > 1:
+                    comps.append(comp)
+    return comps
+
+
+def constant_victims(copies):
+    """The copies the constant policy converts, in conversion order: Kahn's order, and at a stall the lowest-index
+    pending copy.  (The set does not depend on which ready copy pops first.)"""
+    n, rs = len(copies), crwi_ranges(copies)
+    indeg = [0] * n
+    for i, (a, b) in enumerate(rs):
+        for x in range(a, b):
+            indeg[x] += x != i
+    ready, done, victims, low_ptr, left = [i for i in range(n) if indeg[i] == 0], [False] * n, [], 0, n
+    while left:
+        if ready:
+            v = ready.pop()
+        else:
+            while done[low_ptr]:
+                low_ptr += 1
+            v = low_ptr
+            victims.append(v)
+        done[v] = True
+        left -= 1
+        for x in range(*rs[v]):
+            if x != v and not done[x]:
+                indeg[x] -= 1
+                if indeg[x] == 0:
+                    ready.append(x)
+    return victims
+
+
+def victim_bound(d, policy):
+    """An upper bound of the victims' payload bytes: exact under the constant policy; under localmin a victim is
+    the smallest copy of a cycle, so of a component every copy but its one longest may be converted."""
+    copies = copies_of(d)
+    if policy == "constant":
+        return sum(copies[v][2] for v in constant_victims(copies))
+    total = 0
+    for comp in crwi_sccs(copies):
+        lens = sorted(copies[v][2] for v in comp)
+        total += sum(lens) - (lens[-1] if lens[-1] > lens[-2] else 0)
+    return total
+
+
+def in_window(src, n):
+    """R[src, src + n) lies wholly inside one of R's windows of random bytes."""
+    return n > 0 and any(o <= src and src + n <= o + len(b) for o, b in R.windows())
+
+
+def inplace_size(d, victims):
+    """The size of the in-place form of standard delta d when the copies `victims` (indices) are converted."""
+    st, copies = sm.Stream.of(d), copies_of(d)
+    adds = [n for kind, _, _, n in st.cmds if kind == 2]
+    return 25 + 13 * (len(copies) - len(victims)) + sum(9 + n for n in adds) + sum(9 + copies[v][2] for v in victims) + 1
+
+
+def _identity(lengths, at=0):
+    """COPYs with src == dst, one after the other from `at`: each reads only what it writes itself."""
+    cmds = []
+    for n in lengths:
+        cmds.append(("C", at, n))
+        at += n
+    return cmds
+
+
+def inplace_cases():
+    rng = random.Random(0x233A)
+    out, refusals = [], []
+
+    def add(name, ref_len, d, status=OK, host=None, only=POLICIES, into=None):
+        d = d if isinstance(d, bytes) else sstream(d)
+        st = {p: status for p in only}
+        st["host"] = status if host is None else host
+        (out if into is None else into).append((name, ref_len, d, st))
+
+    def shuffled(ls):
+        ls = list(ls)
+        rng.shuffle(ls)
+        return ls
+
+    # refusals, each the only defect of its stream; each goes between two good streams (below)
+    for e in LOW:
+        add(f"refuse_src_len_past_ref_{e:#x}", e, stream([("C", 0, 0, e - 1), ("C", e - 1, e - 1, 2)], e + 1), MALFORMED,
+            into=refusals)
+    add("refuse_src_len_2p32", RLEN, stream([("C", U32 - 16, 0, 16)], 16), MALFORMED, into=refusals)
+    add("refuse_src_len_2p32_plus_16", RLEN, stream([("C", U32 - 16, 0, 32)], 32), MALFORMED, into=refusals)
+    # the host converter takes no dst field as it is: it sorts the commands by dst and places them itself
+    add("refuse_dst_off_by_one", RLEN, stream([("C", 0, 0, H), ("C", 5, H + 1, 8)], H + 9), UNSUPPORTED, host=OK, into=refusals)
+    # every dst field is the running sum mod 2^32: a 32-bit compare accepts it.  The host converter sorts the
+    # third command in front of the second, places all three and answers DG_OK (include/delta_gpu.h)
+    add("refuse_sum_2p32_plus_16", RLEN, stream([("C", 0, 0, H), ("C", 5, H, H), ("C", 0, U32, 16)], 16), UNSUPPORTED, host=OK,
+        into=refusals)
+
+    # identity tilings: no edge, the output order is the rank.  One with every length of IP_LENGTHS (4 radix
+    # passes), one of 128 copies (two lane batches), and one each whose longest copy needs 1, 2 and 3 passes
+    assert sum(IP_LENGTHS) == 3354592519 < RLEN
+    add("identity_4_passes", RLEN, _identity(shuffled(IP_LENGTHS)))
+    add("identity_4_passes_128", RLEN, _identity(shuffled(IP_LENGTHS + [rng.randrange(1, 1 << 20) for _ in range(111)])))
+    for (passes, base), e in zip(((1, [1, 7, 255, 255, 254, 128]),
+                                  (2, [1, 7, 255, 256, 256, 257, 65535, 65535, 0x0134, 0x0234, 0xFF00, 0x00FF]),
+                                  (3, [255, 256, 257, 65535, 65536, 65536, 65537, (1 << 24) - 1, 0x010203, 0x020203, 0xFF0000])), LOW):
+        ls = base + [rng.randrange(1, 1 << (8 * passes)) for _ in range(70 - len(base))]
+        assert 1 << (8 * passes - 8) <= max(ls) < 1 << (8 * passes)
+        add(f"identity_{passes}_passes", e, _identity(shuffled(ls)))
+
+    # the same lengths followed by a short tail whose COPYs read what the tiling writes: edges, so the lengths go
+    # through the Kahn loop; dst, dst + len and version_size on every member of E
+    for e in E:
+        ls = shuffled(IP_LENGTHS[:-1])                            # below 2^31 together
+        at = sum(ls)
+        if e in LOW:
+            cmds = _identity(ls) + [("C", at, e - 64 - at), ("C", 12345, 20), ("A", rng.randbytes(3)), ("C", 5, 40),
+                                    ("C", H // 2 + 7, 1)]
+        else:
+            cmds = _identity(ls) + [("C", at, H - 1 - at), ("C", H - 1, 1), ("C", H, 1), ("C", H + 1, RLEN - 4 - (H + 1))]
+            at = RLEN - 4 + (1 << 19) + 5 + 64
+            cmds += [("C", 12345, 1 << 19), ("A", rng.randbytes(5)), ("C", H - 33, 64), ("C", 3, e - 1 - at), ("C", H // 2 + 7, 1)]
+            if e == U32 - 1:
+                cmds.append(("C", 7, 0))                          # dst = 0xFFFFFFFF
+        assert seq(cmds)[1] == e
+        add(f"tail_{e:#x}", min(e, RLEN), cmds)
+        if e in LOW:
+            out.append(refusals.pop(0))
+
+    # covering() streams: localmin only
+    for e in LOW:
+        add(f"covering_ref_{e:#x}", e, covering(rng, e, top=e - 8000)[0], only=("localmin",))
+    add("covering_whole_r", RLEN, covering(rng, RLEN)[0], only=("localmin",))
+    for t in edge_targets():   # the first command at dst 2^31 behind an edge of the 1 KiB parse window (and of the others)
+        add(f"edge_{t}", RLEN, covering(rng, RLEN, target=t, n_small=1000 if t < 5000 else 420)[0], only=("localmin",))
+    out.append(refusals.pop(0))
+
+    # cycles above 2^31: tests/inplace_graphs.py's, scaled to fit a window of R; the blocks at dst >= 2^31 behind
+    # one identity COPY, every source inside the window, so a victim's payload is random bytes
+    shapes = {
+        "swap_equal": [(8, 8), (0, 8)],
+        "swap_unequal": [(10, 20), (0, 10)],
+        "rotate_3": [(8, 8), (16, 8), (0, 8)],
+        "rotate_8": [(3 * ((k + 1) % 8), 3) for k in range(8)],
+        "reverse_8": [(27, 3), (22, 5), (18, 4), (11, 7), (5, 6), (3, 2), (1, 2), (0, 1)],
+        "two_sccs_linked": [(4, 4), (0, 4), (2, 4), (16, 4), (10, 4)],
+        "figure_eight": [(15, 15), (0, 11), (11, 4)],
+    }
+    for k, (name, blocks) in enumerate(shapes.items()):
+        for w in (IP_WINDOWS[k % 3], IP_WINDOWS[(k + 1) % 3]):
+            base = max(w, H)                                      # (the window at 2^31 - 33: from 2^31 on)
+            assert sum(n for _, n in blocks) <= 30
+            cmds = [("C", 0, base)] + [("C", base + o, n) for o, n in blocks]
+            assert all(in_window(c[1], c[2]) for c in cmds[1:])
+            add(f"{name}_at_{base:#x}", RLEN, cmds)
+        if k in (1, 4):
+            out.append(refusals.pop(0))
+
+    # touching intervals: a two-cycle that exists only with the one-byte overlap
+    for w in LOW:
+        for ov in (0, 1):
+            # hi: A writes [w - 10, w) and reads up to w (+ 1: into B's write); B writes from w and reads A's write
+            add(f"hi_touch_{w:#x}_{ov}", RLEN, [("C", 0, w - 10), ("C", w - 10 + ov, 10), ("C", w - 8, 5)])
+            # pred: A writes [w - 10, w) and reads B's write; B writes from w and reads from w (- 1: the last byte A writes)
+            add(f"pred_touch_{w:#x}_{ov}", RLEN, [("C", 0, w - 10), ("C", w, 10), ("C", w - ov, 5)])
+            IP_VICTIMS[f"hi_touch_{w:#x}_{ov}"] = IP_VICTIMS[f"pred_touch_{w:#x}_{ov}"] = ov
+    for ov in (0, 1):   # J, the last copy, writes [RLEN - 100, 2^32 - 1); A reads up to RLEN - 100 (+ 1); J reads A's write
+        add(f"end_touch_{ov}", RLEN, [("C", 0, H), ("C", RLEN - 110 + ov, 10), ("C", H + 10, RLEN - 100 - (H + 10)),
+                                      ("C", H, U32 - 1 - (RLEN - 100))])
+        IP_VICTIMS[f"end_touch_{ov}"] = ov
+        # the same with J's write ending at 2^32 itself, and A reading from one byte behind J's first: J is then the
+        # write that starts before A's read interval and reaches into it, which dst[j] + len[j] decides, a sum that
+        # no longer fits 32 bits.  The lengths sum to 2^32, which no command follows, so every dst is in place; the
+        # header's version_size is the sum mod 2^32, 0.  The device plan, dg_make_inplace and the reference convert it
+        add(f"end_touch_2p32_{ov}", RLEN, [("C", 0, H), ("C", RLEN - 110 + 11 * ov, 10), ("C", H + 10, RLEN - 100 - (H + 10)),
+                                           ("C", H, U32 - (RLEN - 100))])
+        IP_VICTIMS[f"end_touch_2p32_{ov}"] = ov
+    out.append(refusals.pop(0))
+    add("closing_swap", RLEN, [("C", 0, IP_WINDOWS[1]), ("C", IP_WINDOWS[1] + 5, 5), ("C", IP_WINDOWS[1], 5)])
+    assert not refusals and out[0][3]["host"] == OK == out[-1][3]["host"]
+
+    # the bounds on work, and the victims that read random bytes
+    in_windows = 0
+    for name, ref_len, d, st in out:
+        if st["host"] != OK or UNSUPPORTED in st.values():
+            continue
+        copies = copies_of(d)
+        for p in POLICIES:
+            assert p not in st or victim_bound(d, p) <= IP_VICTIM_MAX, (name, p)
+        # a component all of whose copies read inside a window gives at least one such victim, whichever it is
+        in_windows += sum(1 for comp in crwi_sccs(copies) if all(in_window(copies[v][0], copies[v][2]) for v in comp))
+    assert in_windows >= 12, in_windows
+    return out
+
+
+def inplace_list(policy):
+    """The cases of one policy's batch, in corpus order: a refusal always lies between two accepted streams."""
+    cases = [c for c in corpus()["inplace"] if policy in c[3]]
+    for k, c in enumerate(cases):
+        assert c[3][policy] == OK or (0 < k < len(cases) - 1 and cases[k - 1][3][policy] == OK == cases[k + 1][3][policy]), c[0]
+    return cases
+
+
+def inplace_capacity_cases():
+    """(name, ref_len, standard delta, {policy: size}): streams with one victim of about 2^31 bytes, which
+    nothing here converts: they run last in a batch whose out_cap ends a few KiB behind the good outputs, get
+    DG_ERR_CAPACITY, and their sizes still count in the packed offsets.  size: of the in-place form, from the
+    command list.  Two such sizes stay below 2^32 together, so there are three exchanges, for the offsets to
+    pass 2^32 under either policy: V = R[RLEN - a, RLEN) + R[0, b), a two-cycle whose victim is the shorter
+    copy, the first of equals (localmin), or the first (constant).  The covering() stream is the constant
+    policy's alone: its lowest-index pending copy is the one of 2 GiB, which lies on no cycle."""
+    out = []
+    for name, a, b in (("exchange_short_first", RLEN - H, H), ("exchange_long_first", H, H - 1), ("exchange_equal", H - 1, H - 1)):
+        d = sstream([("C", RLEN - a, a), ("C", 0, b)])
+        assert crwi_sccs(copies_of(d)) == [[1, 0]] and constant_victims(copies_of(d)) == [0]
+        out.append((name, RLEN, d, {"localmin": inplace_size(d, [0 if a <= b else 1]), "constant": inplace_size(d, [0])}))
+    d = covering(random.Random(0x233B), RLEN)[0]
+    copies, victims = copies_of(d), constant_victims(copies_of(d))
+    assert sum(1 for v in victims if copies[v][2] > IP_VICTIM_MAX) == 1 and copies[victims[0]][2] == H - 3
+    out.append(("covering_constant", RLEN, d, {"constant": inplace_size(d, victims)}))
+    for p in POLICIES:
+        assert all(H - (1 << 21) < c[3][p] < H + (1 << 16) for c in out if p in c[3])
+        assert sum(c[3][p] for c in out if p in c[3]) > U32
+    return out
+
+
 
 _cache = {}
 
@@ -721,7 +1027,7 @@ _cache = {}
 def corpus():
     if not _cache:
         _cache.update(compose=compose_cases(), invert=invert_cases(), read=read_cases(), splice=splice_cases(),
-                      decode=decode_cases(), update=update_cases(), lineage=lineage_cases())
+                      decode=decode_cases(), update=update_cases(), lineage=lineage_cases(), inplace=inplace_cases())
     return _cache
 
 
@@ -749,6 +1055,10 @@ def reach():
             if case[3] == OK:
                 _fields(case[2], out[op])
                 out[op]["ref_len"].add(case[1])
+    for _, ref_len, d, st in c["inplace"]:
+        if OK in (st.get("localmin"), st.get("constant")):
+            _fields(d, out["inplace"])
+            out["inplace"]["ref_len"].add(ref_len)
     for _, whole, segs, deltas, _, st in c["splice"]:
         if st == OK:   # of the spliced delta: sources rebased, dst in the whole V
             into = out["splice"]

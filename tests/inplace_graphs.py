@@ -80,6 +80,36 @@ def named_graphs():
     return out
 
 
+SEAM_SIZES = (2047, 2048, 2049, 65535, 65536, 65537)
+
+
+def seam_graphs():
+    """Graphs at the storage seams of the device's order kernel, kept apart from named_graphs() because they
+    are larger: the dst column is cached in LDS up to 2048 copies, and the ready bitmap lies in LDS up to 2048
+    words, 65536 copies (kLdsWords of dg_inplace_dev.hip).  Pinned in tests/golden/golden_inplace_seams.json."""
+    out = []
+
+    def g(name, seed, r_len, cmds, **params):
+        out.append((name, dict(seed=seed, r_len=r_len, **params), _r(seed, r_len), cmds))
+
+    for n in SEAM_SIZES:   # permutations of 4-byte blocks, one block repeated where R has one too few
+        rng = random.Random(0x9E3700 + n)
+        r_len = 16384 if n < 4096 else 1 << 18
+        nb = min(n, r_len // 4)
+        perm = list(range(nb))
+        rng.shuffle(perm)
+        if n > nb:
+            perm += [rng.randrange(nb) for _ in range(n - nb)]
+        g(f"perm_{n}", 100 + n, r_len, [("copy", 4 * b, 4) for b in perm], copies=n)
+    # lengths on both sides of 2^8 and 2^16, so three radix passes, on the Kahn path and with victims: six
+    # blocks rotated left by one, then two exchanges of neighbours; then six copies that read the rotation's
+    # blocks and that nothing reads: ready from the start, they pop in rank order before all others
+    sizes = [65536, 255, 65537, 256, 65535, 257, 256, 65536, 65535, 257]
+    g("radix_edges", 30, 400 * 1024, _blocks([1, 2, 3, 4, 5, 0, 7, 6, 9, 8], sizes) +
+      [("copy", 100 * k, n) for k, n in enumerate([257, 65536, 255, 65537, 256, 65535])])
+    return out
+
+
 def build(dg, orc, R, cmds):
     """(standard delta, V) of a recipe: place_commands + encode_delta."""
     cl = [dg.CopyCmd(c[1], c[2]) if c[0] == "copy" else dg.AddCmd(c[1]) for c in cmds]

@@ -8,9 +8,13 @@
 // from the resulting order must equal dg_make_inplace's (dg_inplace.cpp, which
 // keeps explicit adjacency lists: an independent implementation).
 //
-// Input: a corpus file of records (u32 |R|, R, u32 |delta|, delta), little
-// endian, each converted under both policies; then `random` more seeded random
-// command lists are built here.  Prints "checked N failures F".
+// Input: a corpus file of records, little endian: the reference, either dense
+// (u32 0, u32 |R|, R) or sparse (u32 1, u64 |R|, u32 windows, then per window
+// u64 offset, u32 bytes, the bytes: zero everywhere else, held in an anonymous
+// mapping whose untouched pages cost nothing, so an R of 4 GiB is cheap); then
+// u32 |delta|, delta, and u32 policies (bit p: converted under policy p).  Then
+// `random` more seeded random command lists are built here, converted under both
+// policies.  Prints "checked N failures F".
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -18,6 +22,8 @@
 #include <cstring>
 #include <numeric>
 #include <vector>
+
+#include <sys/mman.h>
 
 #include "../../delta-compression_amd/csrc/dg_inplace_core.h"
 #include "../../include/delta_gpu.h"
@@ -30,7 +36,7 @@ void put_be32(std::vector<uint8_t>& o, uint64_t x) {
 
 // The conversion through the shared core; false: the delta is not one the
 // device converts (commands not placed sequentially), nothing to compare.
-bool convert_core(const std::vector<uint8_t>& R, const std::vector<uint8_t>& delta, int policy,
+bool convert_core(const uint8_t* R, size_t r_len, const std::vector<uint8_t>& delta, int policy,
                   std::vector<uint8_t>& out) {
 	dg_commands_t cl{};
 	if (dg_delta_decode(delta.data(), delta.size(), &cl, nullptr) != DG_OK) return false;
@@ -42,7 +48,7 @@ bool convert_core(const std::vector<uint8_t>& R, const std::vector<uint8_t>& del
 		const dg_placed_command_t& c = cl.data[k];
 		if (c.dst != wpos) ok = false;
 		if (c.tag == DG_CMD_COPY) {
-			if (c.src + c.length > R.size()) ok = false;
+			if (c.src + c.length > r_len) ok = false;
 			src.push_back((uint32_t)c.src);
 			dst.push_back((uint32_t)c.dst);
 			len.push_back((uint32_t)c.length);
@@ -89,7 +95,7 @@ bool convert_core(const std::vector<uint8_t>& R, const std::vector<uint8_t>& del
 		out.push_back(2);
 		put_be32(out, dst[v]);
 		put_be32(out, len[v]);
-		out.insert(out.end(), R.begin() + src[v], R.begin() + src[v] + len[v]);
+		out.insert(out.end(), R + src[v], R + src[v] + len[v]);
 	}
 	out.push_back(0);
 	dg_commands_free(&cl);
@@ -139,6 +145,19 @@ void random_case(std::vector<uint8_t>& R, std::vector<uint8_t>& delta) {
 	dg_buffer_free(&b);
 }
 
+struct Case {
+	std::vector<uint8_t> dense;   // R, or
+	struct Window {
+		uint64_t off;
+		std::vector<uint8_t> bytes;
+	};
+	std::vector<Window> windows;  // what of a sparse R is not zero
+	uint64_t r_len = 0;
+	bool sparse = false;
+	std::vector<uint8_t> delta;
+	uint32_t policies = 3;
+};
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -146,39 +165,72 @@ int main(int argc, char** argv) {
 		fprintf(stderr, "usage: %s corpus.bin n_random\n", argv[0]);
 		return 2;
 	}
-	std::vector<std::pair<std::vector<uint8_t>, std::vector<uint8_t>>> cases;
+	std::vector<Case> cases;
 	FILE* f = fopen(argv[1], "rb");
 	if (!f) return 2;
 	for (;;) {
-		uint32_t rl, dl;
-		if (fread(&rl, 4, 1, f) != 1) break;
-		std::vector<uint8_t> R(rl);
-		if (rl && fread(R.data(), 1, rl, f) != rl) return 2;
+		uint32_t tag, dl;
+		if (fread(&tag, 4, 1, f) != 1) break;
+		Case c;
+		if (tag == 0) {
+			uint32_t rl;
+			if (fread(&rl, 4, 1, f) != 1) return 2;
+			c.dense.resize(rl);
+			if (rl && fread(c.dense.data(), 1, rl, f) != rl) return 2;
+			c.r_len = rl;
+		} else if (tag == 1) {
+			uint32_t nw;
+			c.sparse = true;
+			if (fread(&c.r_len, 8, 1, f) != 1 || fread(&nw, 4, 1, f) != 1) return 2;
+			for (uint32_t k = 0; k < nw; ++k) {
+				Case::Window w;
+				uint32_t nb;
+				if (fread(&w.off, 8, 1, f) != 1 || fread(&nb, 4, 1, f) != 1) return 2;
+				w.bytes.resize(nb);
+				if (nb && fread(w.bytes.data(), 1, nb, f) != nb) return 2;
+				if (w.off + nb > c.r_len) return 2;
+				c.windows.push_back(std::move(w));
+			}
+		} else {
+			return 2;
+		}
 		if (fread(&dl, 4, 1, f) != 1) return 2;
-		std::vector<uint8_t> d(dl);
-		if (dl && fread(d.data(), 1, dl, f) != dl) return 2;
-		cases.emplace_back(std::move(R), std::move(d));
+		c.delta.resize(dl);
+		if (dl && fread(c.delta.data(), 1, dl, f) != dl) return 2;
+		if (fread(&c.policies, 4, 1, f) != 1) return 2;
+		cases.push_back(std::move(c));
 	}
 	fclose(f);
 	const int n_random = atoi(argv[2]);
 	for (int k = 0; k < n_random; ++k) {
 		cases.emplace_back();
-		random_case(cases.back().first, cases.back().second);
+		random_case(cases.back().dense, cases.back().delta);
+		cases.back().r_len = cases.back().dense.size();
 	}
 	size_t checked = 0, failures = 0, victims_seen = 0;
 	for (size_t i = 0; i < cases.size(); ++i) {
+		const Case& c = cases[i];
+		const uint8_t* R = c.dense.data();
+		void* map = nullptr;
+		if (c.sparse && c.r_len) {
+			map = mmap(nullptr, c.r_len, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS | MAP_NORESERVE, -1, 0);
+			if (map == MAP_FAILED) return 2;
+			for (const auto& w : c.windows) memcpy((uint8_t*)map + w.off, w.bytes.data(), w.bytes.size());
+			R = (const uint8_t*)map;
+		}
+		const size_t r_len = c.r_len;
+		const auto& d = c.delta;
 		for (int policy = 0; policy < 2; ++policy) {
-			const auto& R = cases[i].first;
-			const auto& d = cases[i].second;
+			if (!(c.policies >> policy & 1)) continue;
 			std::vector<uint8_t> got;
-			if (!convert_core(R, d, policy, got)) {
+			if (!convert_core(R, r_len, d, policy, got)) {
 				fprintf(stderr, "case %zu: not a sequential standard delta\n", i);
 				++failures;
 				continue;
 			}
 			dg_buffer_t exp{nullptr, 0};
 			dg_inplace_stats_t st{};
-			const int rc = dg_make_inplace(R.data(), R.size(), d.data(), d.size(), policy, &exp, &st);
+			const int rc = dg_make_inplace(R, r_len, d.data(), d.size(), policy, &exp, &st);
 			if (rc != DG_OK || exp.len != got.size() || memcmp(exp.data, got.data(), got.size()) != 0) {
 				fprintf(stderr, "case %zu policy %d: core differs from dg_make_inplace (rc %d, %zu vs %zu bytes)\n", i,
 				        policy, rc, exp.len, got.size());
@@ -188,6 +240,7 @@ int main(int argc, char** argv) {
 			dg_buffer_free(&exp);
 			++checked;
 		}
+		if (map) munmap(map, c.r_len);
 	}
 	printf("checked %zu failures %zu adds %zu\n", checked, failures, victims_seen);
 	return failures ? 1 : 0;

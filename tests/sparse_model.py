@@ -450,6 +450,20 @@ def update_status(ref_len: int, delta: bytes, buf_cap: int):
     return OK if st.inplace else UNSUPPORTED
 
 
+def inplace_status(ref_len: int, delta: bytes):
+    """dg_inplace_plan_run's per-stream status for a standard delta of at most one defect: malformed framing or a
+    COPY past R, then commands that are not placed one after the other (the sum taken in 64 bits)."""
+    st = Stream.of(delta)
+    if not st.framing or st.copy_past(ref_len):
+        return MALFORMED
+    at = 0
+    for _, _, dst, n in st.cmds:
+        if dst != at:
+            return UNSUPPORTED
+        at += n
+    return OK
+
+
 def read(R, delta: bytes, off: int, length: int):
     """dg_read: (status, bytes [off, off + n)) with pread's n."""
     R = SparseBytes.of(R)

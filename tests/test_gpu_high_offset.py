@@ -16,6 +16,9 @@ levels on R name prefixes of the arena, the others state their parent's size.
 Decode and update run without CRC checks (one block would
 checksum 4 GiB); the decode_large test runs with them, on a version of
 2^31 + 2^20 + 3 bytes whose expected CRC comes from the model's combine.
+InplacePlan is driven directly too, one batch per policy: its expected bytes
+are the reference's own (tests/golden/golden_inplace_high.json), not the
+model's, and dg_make_inplace is computed only to describe a difference.
 
 Device memory: 4 GiB for R, and about 4.2 GiB more while the decode_large test
 compares its output (2 GiB of output plus the compare's temporary).
@@ -23,7 +26,11 @@ compares its output (2 GiB of output plus the compare's temporary).
 from __future__ import annotations
 
 import ctypes as C
+import hashlib
+import json
+import os
 import struct
+import time
 
 import numpy as np
 import pytest
@@ -39,6 +46,8 @@ from test_gpu_splice import Run as SpliceRun
 pytestmark = pytest.mark.gpu
 
 OK, TOO_LARGE, CAPACITY, DST_CRC = 0, 3, 7, 10
+GOLD_INPLACE = {(c["name"], c["policy"]): c for c in json.load(open(os.path.join(
+    os.path.dirname(os.path.abspath(__file__)), "golden", "golden_inplace_high.json")))["cases"]}
 GUARD = 0xA5
 HEAD = 1 << 17   # what an update of this corpus may change of the arena: its versions are below 64 KiB
 
@@ -393,3 +402,109 @@ def test_read_lineage_batch_equals_read_lineage(dg, ctx, torch_cuda):
         assert (st[k], got[k]) == (e[0], e[1]), (i, off, ln)
         if k % 8 == 0:
             assert dg.read_lineage(host_r, hc.lineage_path(ns, i)[1], off, ln) == got[k], (i, off, ln)
+
+
+# 11. in-place conversion: every case of a policy's list in one plan, against the reference's goldens
+class InplaceRun:
+    """items: (ref_len, standard delta), every reference a prefix of d_ref.  The streams lie at odd offsets of a
+    small arena between guard bytes; the output buffer is out_cap bytes and 4 KiB of guard bytes behind them."""
+    TAIL = 4096
+
+    def __init__(self, torch, dg, ctx, d_ref, items, policy, out_cap):
+        self.torch, self.ctx, self.n, self.out_cap, self.d_ref = torch, ctx, len(items), out_cap, d_ref
+        buf, descs = bytearray(), []
+        for k, (ref_len, d) in enumerate(items):
+            buf += bytes([GUARD]) * (1 + (3 * k) % 15)
+            buf += bytes([GUARD]) * (1 - len(buf) % 2)
+            descs.append((0, ref_len, len(buf), len(d)))
+            buf += d
+        assert all(d[2] % 2 for d in descs)
+        self.plan = dg.InplacePlan(ctx, descs, policy)
+        self.d_delta = torch.frombuffer(buf + bytes([GUARD]), dtype=torch.uint8).cuda()
+        self.out = torch.empty(out_cap + self.TAIL, dtype=torch.uint8, device="cuda")
+        self.off = torch.empty(self.n + 1, dtype=torch.int64, device="cuda")
+        self.st = torch.empty(self.n, dtype=torch.int32, device="cuda")
+
+    def run(self):
+        """(statuses, offsets, the whole output buffer) of one run into buffers filled afresh."""
+        torch = self.torch
+        self.out.fill_(GUARD)
+        self.off.fill_(-1)
+        self.st.fill_(-1)
+        torch.cuda.synchronize()
+        self.plan.run(self.d_ref.data_ptr(), self.d_delta.data_ptr(), self.out.data_ptr(), self.out_cap, self.off.data_ptr(),
+                      self.st.data_ptr(), stream=self.ctx.stream)
+        torch.cuda.synchronize()
+        return self.st.cpu().tolist(), self.off.cpu().tolist(), bytes(self.out.cpu().numpy())
+
+
+def _host_difference(dg, name, ref_len, d, policy, got):
+    """Where the device's bytes leave dg_make_inplace's: computed only when a digest differs."""
+    buf = np.zeros(hc.RLEN, dtype=np.uint8)
+    for o, b in hc.R.windows():
+        buf[o:o + len(b)] = np.frombuffer(b, dtype=np.uint8)
+    out = dg._lib.Buffer()
+    rc_ = dg.lib.dg_make_inplace(buf.ctypes.data_as(C.POINTER(C.c_uint8)), ref_len, dg._lib._u8(d), len(d), dg._lib.POLICIES[policy],
+                                 C.byref(out), None)
+    exp = C.string_at(out.data, out.len) if out.len else b""
+    dg.lib.dg_buffer_free(C.byref(out))
+    at = next((k for k, (x, y) in enumerate(zip(got, exp)) if x != y), min(len(got), len(exp)))
+    return (f"{name} ({policy}): the device's {len(got)} bytes leave dg_make_inplace's {len(exp)} (rc {rc_}) at byte {at}: "
+            f"{got[at:at + 26].hex()} for {exp[at:at + 26].hex()}")
+
+
+def _check_inplace(dg, policy, cases, st, offs, out, good_total):
+    """Statuses, packed offsets and bytes of the accepted and refused streams at the front of a batch."""
+    at = 0
+    for k, (name, ref_len, d, sts) in enumerate(cases):
+        assert st[k] == sts[policy], (name, st[k])
+        assert offs[k] == at, name
+        if sts[policy] == OK:
+            g = GOLD_INPLACE[(name, policy)]
+            got = out[at:at + g["len"]]
+            assert offs[k + 1] - at == g["len"], (name, offs[k + 1] - at, g["len"])
+            assert hashlib.sha256(got).hexdigest() == g["sha256"], _host_difference(dg, name, ref_len, d, policy, got)
+            at += g["len"]
+    assert at == good_total == offs[len(cases)]
+    assert out[at:] == bytes([GUARD]) * (len(out) - at), "a byte behind the outputs changed"
+
+
+@pytest.mark.parametrize("policy", hc.POLICIES)
+def test_inplace_plan(dg, ctx, torch_cuda, arena, policy):
+    cases = hc.inplace_list(policy)
+    assert sum(1 for c in cases if c[3][policy] != OK) == 7
+    total = sum(GOLD_INPLACE[(c[0], policy)]["len"] for c in cases if c[3][policy] == OK)
+    r = InplaceRun(torch_cuda, dg, ctx, arena, [(c[1], c[2]) for c in cases], policy, total + 100)
+    t0 = time.perf_counter()
+    st, offs, out = r.run()
+    print(f"inplace high-offset batch ({policy}): {len(cases)} streams, {time.perf_counter() - t0:.3f} s")
+    _check_inplace(dg, policy, cases, st, offs, out, total)
+    assert (st, offs, out) == r.run(), "a second run of the same plan differs"
+
+
+# 12. out_cap decides: victims of about 2^31 bytes each behind good streams take the packed offsets past 2^32
+@pytest.mark.parametrize("policy", hc.POLICIES)
+def test_inplace_plan_capacity(dg, ctx, torch_cuda, arena, policy):
+    good = hc.inplace_list(policy)[:24]
+    while good[-1][3][policy] != OK:
+        good.pop()
+    assert len(good) >= 20 and sum(1 for c in good if c[3][policy] != OK) >= 3
+    caps = [c for c in hc.inplace_capacity_cases() if policy in c[3]]
+    assert len(caps) == {"localmin": 3, "constant": 4}[policy]
+    total = sum(GOLD_INPLACE[(c[0], policy)]["len"] for c in good if c[3][policy] == OK)
+    out_cap = total + 3000
+    if policy == "constant":
+        # one more, behind the first: the constant policy converts the first copy of an exchange whatever its length, so
+        # its length can put this stream's end at 2^32 + 1500: an end kept in 32 bits would lie inside out_cap
+        a = hc.U32 + 1500 - (total + caps[0][3][policy]) - 48
+        d = hc.sstream([("C", hc.RLEN - a, a), ("C", 0, 8)])
+        assert hc.H < a < hc.RLEN and hc.constant_victims(hc.copies_of(d)) == [0] and hc.inplace_size(d, [0]) == a + 48
+        caps.insert(1, ("exchange_end_at_2p32_plus_1500", hc.RLEN, d, {policy: a + 48}))
+    r = InplaceRun(torch_cuda, dg, ctx, arena, [(c[1], c[2]) for c in good + caps], policy, out_cap)
+    st, offs, out = r.run()
+    _check_inplace(dg, policy, good, st, offs, out, total)   # every earlier stream exact, and no byte behind them changed
+    assert st[len(good):] == [CAPACITY] * len(caps)
+    for k, c in enumerate(caps, len(good)):
+        assert offs[k + 1] - offs[k] == c[3][policy], (c[0], offs[k + 1] - offs[k], c[3][policy])
+    assert offs[-1] > hc.U32
+    assert policy != "constant" or offs[len(good) + 2] - hc.U32 == 1500 < out_cap

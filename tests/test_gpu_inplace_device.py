@@ -17,7 +17,7 @@ import pytest
 
 import window_cases as wc
 
-from inplace_graphs import POLICIES, build, named_graphs
+from inplace_graphs import POLICIES, build, named_graphs, seam_graphs
 from stage_timing import check_ring_phases
 from test_oracle import inplace_inputs
 
@@ -26,6 +26,8 @@ pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLD = {(c["name"], c["policy"]): c
         for c in json.load(open(os.path.join(HERE, "golden", "golden_inplace_graphs.json")))["cases"]}
+SEAM_GOLD = {(c["name"], c["policy"]): c
+             for c in json.load(open(os.path.join(HERE, "golden", "golden_inplace_seams.json")))["cases"]}
 OLD = json.load(open(os.path.join(HERE, "golden", "golden_inplace.json")))["cases"]
 OK, UNSUPPORTED, CAPACITY, MALFORMED = 0, 2, 7, 8
 ALGO = {1: "onepass", 2: "correcting"}
@@ -351,3 +353,49 @@ def test_parse_window_edges(dg, ctx, orc, torch_cuda):
     assert st == [OK] * len(items)
     for (name, *_), (R, d), got in zip(wc.standard_cases(dg, orc), items, outs):
         assert got == dg.make_inplace(R, d, "localmin"), name
+
+
+# 10. the storage seams of the order kernel (tests/inplace_graphs.py seam_graphs): the dst column in LDS up to 2048
+#     copies, the ready bitmap in LDS up to 65536 copies and in work memory above; three radix passes on the Kahn
+#     path.  One batch per policy, a small graph before and after, against the reference's goldens
+@pytest.fixture(scope="module")
+def seams(dg, orc):
+    return [(name, R, *build(dg, orc, R, cmds)) for name, _, R, cmds in seam_graphs()]
+
+
+def _first_difference(dg, name, R, std, policy, got):
+    exp = dg.make_inplace(R, std, policy)   # computed only to describe a difference
+    at = next((k for k, (x, y) in enumerate(zip(got, exp)) if x != y), min(len(got), len(exp)))
+    return f"{name} ({policy}): {len(got)} bytes for {len(exp)}, the first difference at byte {at}: {got[at:at + 26].hex()} for {exp[at:at + 26].hex()}"
+
+
+@pytest.mark.parametrize("policy", POLICIES)
+def test_seam_graphs(dg, ctx, torch_cuda, graphs, seams, policy):
+    small = {g[0]: g for g in graphs}
+    batch = [small["figure_eight"]] + seams + [small["reverse_8"]]
+    gold = [(GOLD if name in small else SEAM_GOLD)[(name, policy)] for name, *_ in batch]
+    times = {}
+    st, outs, offs, _ = _run(torch_cuda, dg, ctx, [(R, std) for _, R, std, _ in batch], policy, out_cap=sum(g["len"] for g in gold),
+                             timing=True, after=lambda plan, go: times.update(plan.stage_times()))
+    print(f"seam graphs ({policy}): stage times in ms {times}")
+    assert st == [OK] * len(batch), dict(zip([g[0] for g in batch], st))
+    assert offs[-1] == sum(g["len"] for g in gold)
+    for (name, R, std, V), got, g in zip(batch, outs, gold):
+        assert len(got) == g["len"] and hashlib.sha256(got).hexdigest() == g["sha256"], _first_difference(dg, name, R, std, policy, got)
+    k = [name for name, *_ in batch].index("perm_65537")
+    assert dg.decode(batch[k][1], outs[k], ctx=ctx) == batch[k][3]
+    # and through the host-buffer entry point
+    for (name, R, std, V), got, g in zip(batch, dg.make_inplace_batch([(R, std) for _, R, std, _ in batch], policy, ctx=ctx), gold):
+        assert len(got) == g["len"] and hashlib.sha256(got).hexdigest() == g["sha256"], _first_difference(dg, name, R, std, policy, got)
+
+
+# 11. the order stage of the 65 537-copy graph alone (one lane runs Tarjan over its vertices in work memory)
+def test_seam_order_stage_time(dg, ctx, torch_cuda, seams):
+    name, R, std, V = next(s for s in seams if s[0] == "perm_65537")
+    g = SEAM_GOLD[(name, "localmin")]
+    times = {}
+    st, outs, _, _ = _run(torch_cuda, dg, ctx, [(R, std)], "localmin", out_cap=g["len"], timing=True,
+                          after=lambda plan, go: times.update(plan.stage_times()))
+    print(f"perm_65537 alone (localmin): stage times in ms {times}")
+    assert st == [OK] and hashlib.sha256(outs[0]).hexdigest() == g["sha256"]
+    assert times["order"] > 0 and times["total"] >= times["order"]
